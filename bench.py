@@ -11,6 +11,9 @@ GPU: `--gpus N` without a torchrun environment starts the N ranks itself (and re
 has fewer GPUs); weights are broadcast once from rank 0 (RCCL), then every rank decodes its own
 utterance shard with no collective in the loop (weak scaling).
 
+`--dump-outputs DIR` writes what the last timed step returned (see dump_outputs); the timed steps draw their noise
+from a generator reseeded when the timed region starts, so the same arguments give the same outputs on every run.
+
 Prints ONE JSON line on rank 0 (see the driver contract).  Extra keys:
   roofline     dominant kernel = the MRF ResBlock conv stack (conv_mfma_kernel), timed live with
                HIP events recorded on the launch stream inside the timed steps
@@ -36,10 +39,17 @@ F32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dens
 HBM_PEAK_GBS = 8000.0
 
 
+def positive_int(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"must be at least 1, got {v}")
+    return n
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=positive_int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="baker", choices=["baker", "multilingual", "aishell3",
                                                           "stress48k"],
@@ -78,6 +88,9 @@ def parse_args():
                     help="f32 decoder: the three ResBlock chains of a stage on ONE stream (WETTS_DECODER_SERIAL; the "
                          "form whose kernel trace has non-overlapping per-kernel durations)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (each sub-batch's audio and "
+                         "y_mask) as DIR/<name>.npy in float32, at most 64 MB in all (see dump_outputs)")
     ap.add_argument("--live-traffic", default="auto", choices=["auto", "0", "1"],
                     help="refresh roofline.traffic by running the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of "
                          "this same command as child processes after the timed region (+ ~1 min).  auto: on for a "
@@ -97,6 +110,36 @@ def parse_args():
     ap.add_argument("--stream-cpu", action="store_true", help="add the CPU-port timing of one window")
     ap.add_argument("--stream-unfused", action="store_true", help="one launch per conv (diagnostic)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(arrays, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """`--dump-outputs DIR`: writes every array of `arrays` ({name: tensor or ndarray}) as DIR/<name>.npy, float64
+    kept, everything else as float32.  When together they would exceed `limit_bytes`, each array is replaced by the
+    same fixed, seeded sample of its flattened elements (sorted indices, a share of the elements proportional to the
+    array's size), so that two builds run with the same arguments write files that compare element for element.
+    Returns {name: {"shape", "dtype", "sampled"}}."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, a in host.items():
+        shape, sampled = list(a.shape), False
+        if total > limit_bytes:
+            keep = int(a.size * (limit_bytes / total))
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+            sampled = True
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": shape, "dtype": str(a.dtype), "sampled": sampled}
+    return info
 
 
 def make_inputs(model_name, n_vocab, n_speakers, total_utts, tx, ragged, seed=0):
@@ -660,6 +703,9 @@ def _bench(args, rank, local_rank, world, mon):
         dist.barrier()
     be.set_mrf_timing(net, True)
     frames = 0.0
+    # the set-up above ran for a time, not a count, of steps: rewind the Philox stream so that the timed steps draw
+    # the same noise on every run with the same arguments (what --dump-outputs compares)
+    torch.manual_seed(1 + rank)
     be.sync()
     t0 = time.perf_counter()
     masks = []
@@ -671,6 +717,12 @@ def _bench(args, rank, local_rank, world, mon):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:  # what the last timed step returned, one array per sub-batch (rank<r>_ prefixed when N > 1)
+        pfx = f"rank{rank}_" if world > 1 else ""
+        last = {f"{pfx}audio_b{i}": a for i, a in enumerate(o)}
+        last.update({f"{pfx}y_mask_b{i}": m for i, m in enumerate(y_masks)})
+        dumped = dump_outputs(last, args.dump_outputs, DUMP_LIMIT_BYTES // world)
     for ym in masks:
         frames += float(ym.sum().item())
     mrf_launched_bytes = be.read_mrf_bytes(net)  # (before the set(.., False) below resets the counters)
@@ -812,10 +864,12 @@ def _bench(args, rank, local_rank, world, mon):
                     if skip:
                         skip = False
                         continue
-                    if a in ("--steps", "--warmup", "--presteps-s", "--live-traffic", "--cpu-sample", "--cpu-fixture"):
+                    if a in ("--steps", "--warmup", "--presteps-s", "--live-traffic", "--cpu-sample", "--cpu-fixture",
+                             "--dump-outputs"):
                         skip = True
                         continue
-                    if a.startswith(("--steps=", "--warmup=", "--presteps-s=", "--live-traffic=")) or a == "--no-cpu-baseline":
+                    if a.startswith(("--steps=", "--warmup=", "--presteps-s=", "--live-traffic=", "--dump-outputs=")) \
+                            or a == "--no-cpu-baseline":
                         continue
                     keep.append(a)
                 child = [os.path.abspath(__file__)] + keep + ["--steps", "1", "--warmup", "1", "--presteps-s", "0.3",
@@ -1001,6 +1055,8 @@ def _bench(args, rank, local_rank, world, mon):
     }
     if be.label:
         out["backend_label"] = be.label
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     sharding.diag("result", n_gpus=observed_world, value=value, ms_per_step=out["ms_per_step"], ranks_seen=ranks_seen,
                   rank_ms=rank_ms, imbalance=out["imbalance"], workload=out["config"]["workload"])
     # contract: the CPU baseline is a rank-0, N = 1 measurement; --cpu-baseline-multi adds it at N > 1 too

@@ -298,6 +298,8 @@ def main():
     if ONLY:
         if "vocos_onnx_stream_kat" in ONLY.split(","):
             vocos_onnx_stream_kat()
+        if "state_dict_kat" in ONLY.split(","):
+            state_dict_kat()
         return
     # MAS known-answer vectors from the reference's maximum_path (numba stub => plain Python)
     _, _, _, mas = ref_import.import_reference()
@@ -338,6 +340,42 @@ def main():
     chunk_kat()
     chunk_kat_triton()
     vocos_onnx_stream_kat()
+    state_dict_kat()
+
+
+# (model config, n_vocab, n_speakers) of the reference modules whose state_dict the CPU tests hold the blob layout to
+STATE_DICT_MODELS = [("v1", 50, 1), ("v3", 50, 2), ("vocos", 50, 2), ("vits2_vocos_v1", 50, 1),
+                     ("tiny_preconv2_spk", 50, 3)]
+
+
+def state_dict_kat():
+    """reference_state_dicts.npz: what tests/test_cpu_host.py compares the module's names, shapes and buffers with.
+    `sd_<model>_<n_speakers>`: the reference SynthesizerTrn(n_vocab, 513, 32)'s state_dict after weight-norm folding,
+    as a JSON {key: shape}; `tiny_rwn_40_3`: the tiny model's own state_dict after dec / flow remove_weight_norm() (what
+    a folded dict is loaded into); `tiny_vocos_onnx_40_2_<buffer>`: the two OnnxSTFT buffers of the is_onnx tiny
+    Vocos module (utils/stft.py:283)."""
+    import json
+    Ref, *_ = ref_import.import_reference()
+
+    def make(mname, n_vocab, n_spk, **ov):
+        with contextlib.redirect_stdout(io.StringIO()):
+            return Ref(n_vocab, 513, 32, n_speakers=n_spk, **dict(config.MODEL_CONFIGS[mname], **ov)).eval()
+
+    def shapes(sd):
+        return np.array(json.dumps({k: list(v.shape) for k, v in sd.items()}))
+
+    out = {}
+    for mname, n_vocab, n_spk in STATE_DICT_MODELS:
+        out[f"sd_{mname}_{n_spk}"] = shapes(checkpoint.fold_weight_norm(make(mname, n_vocab, n_spk).state_dict()))
+    ref = make("tiny", 40, 3)
+    ref.dec.remove_weight_norm()
+    ref.flow.remove_weight_norm()
+    out["tiny_rwn_40_3"] = shapes(ref.state_dict())
+    rsd = make("tiny_vocos", 40, 2, is_onnx=True).state_dict()
+    for k in ("dec.stft.forward_basis", "dec.stft.inverse_basis"):
+        out["tiny_vocos_onnx_40_2_" + k.split(".")[-1]] = rsd[k].numpy()
+    np.savez_compressed(os.path.join(OUT, "reference_state_dicts.npz"), **out)
+    print("reference_state_dicts:", len(out), "entries")
 
 
 def vocos_onnx_stream_kat():

@@ -270,3 +270,61 @@ def test_pmc_traffic_class_sums_and_the_stub_line_never_spawns_a_profiler(tmp_pa
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert "traffic_live" not in d["roofline"]
+
+
+def test_dump_outputs_writes_what_the_last_timed_step_returned(tmp_path):
+    """--dump-outputs DIR: after the timed steps every rank writes the audio and y_mask of each sub-batch of its last
+    timed step (as rank<r>_... when N > 1), float32, named in the JSON line; --steps is the number
+    of timed steps the line reports, with `ms_per_step` beside it."""
+    import numpy as np
+    from wetts_amd import batching
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    p = _run({"WETTS_SCALE_DIAG": os.devnull}, args=["--steps", "3", "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    x, lens, sid = bench.make_inputs("tiny", 256, 218, 16, 128, True)
+    pl = batching.plan(lens.tolist(), 2, max_pad_frac=0.08, ragged=True)
+    hop = d["config"]["hop"]
+    names = sorted(os.listdir(out))
+    want = []
+    for r in (0, 1):
+        pfx = f"rank{r}_"
+        for i, bk in enumerate(pl.buckets[r]):
+            ty = max(int(np.ceil(int(lens[j]) * 6.0 * 0.92)) for j in bk.indices)
+            a, m = np.load(out / f"{pfx}audio_b{i}.npy"), np.load(out / f"{pfx}y_mask_b{i}.npy")
+            assert a.dtype == np.float32 and a.shape == (len(bk), 1, ty * hop)
+            assert m.dtype == np.float32 and m.shape == (len(bk), 1, ty)
+            want += [f"{pfx}audio_b{i}.npy", f"{pfx}y_mask_b{i}.npy"]
+    assert names == sorted(want)
+    assert sorted(d["dumped_outputs"]["arrays"]) == sorted(n[:-4] for n in want if n.startswith("rank0_"))
+    assert sum(os.path.getsize(out / n) for n in names) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_dump_outputs_samples_large_outputs_the_same_way_every_time(tmp_path):
+    """Above the byte limit every array is cut to the same seeded sample of its elements: two dumps of the same arrays
+    are identical, stay within the limit, and hold elements of the original in their original order."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = np.random.default_rng(0)
+    arrays = {"audio_b0": torch.from_numpy(g.standard_normal((4, 1, 5000)).astype(np.float32)),
+              "y_mask_b0": torch.ones(4, 1, 50), "wide": np.arange(3000, dtype=np.float64)}
+    small = bench.dump_outputs(arrays, str(tmp_path / "all"))
+    assert not any(v["sampled"] for v in small.values())
+    assert np.array_equal(np.load(tmp_path / "all" / "audio_b0.npy"), arrays["audio_b0"].numpy())
+    limit = 20000
+    a = bench.dump_outputs(arrays, str(tmp_path / "a"), limit)
+    b = bench.dump_outputs(arrays, str(tmp_path / "b"), limit)
+    assert a == b and all(v["sampled"] for v in a.values())
+    assert a["wide"]["dtype"] == "float64" and a["audio_b0"]["shape"] == [4, 1, 5000]
+    total = 0
+    for n in arrays:
+        x, y = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert np.array_equal(x, y) and x.ndim == 1 and x.size > 0
+        total += x.nbytes
+    assert total <= limit
+    w = np.load(tmp_path / "a" / "wide.npy")
+    assert np.all(np.diff(w) > 0)  # sorted indices into arange: increasing

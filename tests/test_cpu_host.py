@@ -42,19 +42,22 @@ def test_blob_layout_is_consistent(mname):
     assert checkpoint.blob_numel(cfg) >= end
 
 
+REF_STATE_DICTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_state_dicts.npz")
+
+
+def _ref_state_dict(name):
+    """{key: shape} of a reference module's state_dict (tests/golden/make_golden.py:state_dict_kat)."""
+    import json
+    with np.load(REF_STATE_DICTS) as z:
+        return {k: tuple(v) for k, v in json.loads(str(z[name])).items()}
+
+
 def test_layout_names_and_shapes_match_reference_state_dict():
     """Golden list of the reference's own state_dict keys/shapes (dumped from the real
-    SynthesizerTrn in the build container) covers every blob tensor after weight-norm folding."""
-    from oracle import ref_import
-    if not ref_import.available():
-        pytest.skip("reference not present on this box")
-    import contextlib, io
-    S, *_ = ref_import.import_reference()
+    SynthesizerTrn by make_golden.py) covers every blob tensor after weight-norm folding."""
     for mname, nspk in [("v1", 1), ("v3", 2), ("vocos", 2), ("vits2_vocos_v1", 1),
                         ("tiny_preconv2_spk", 3)]:
-        with contextlib.redirect_stdout(io.StringIO()):
-            net = S(50, 513, 32, n_speakers=nspk, **config.MODEL_CONFIGS[mname])
-        ref = {k: tuple(v.shape) for k, v in checkpoint.fold_weight_norm(net.state_dict()).items()}
+        ref = _ref_state_dict(f"sd_{mname}_{nspk}")
         cfg = config.make_config(config.MODEL_CONFIGS[mname], 50, nspk)
         for n, _, _, shape in checkpoint.blob_layout(cfg):
             assert n in ref, n
@@ -181,9 +184,9 @@ def test_triton_min_chunk_helpers_match_the_references_own_functions():
 
 def test_state_dict_round_trip_and_reference_keys():
     """SynthesizerTrn.state_dict(): folded tensors under the reference's keys; loading it into a second model
-    reproduces the blob bit for bit; with the live reference present, the dict loads into the reference module
-    after its own remove_weight_norm() and every tensor lands (CPU tier: read from the host blob; the device
-    read-back through wetts_get_blob is the GPU tier's)."""
+    reproduces the blob bit for bit; the dict loads into the reference module after its own remove_weight_norm()
+    (its keys and shapes: tests/golden/reference_state_dicts.npz) and every tensor lands (CPU tier: read from the host
+    blob; the device read-back through wetts_get_blob is the GPU tier's)."""
     from wetts_amd import SynthesizerTrn
     for mname, n_spk in (("tiny", 3), ("tiny_mono_post", 2), ("tiny_vocos", 2)):
         cfg = config.make_config(config.MODEL_CONFIGS[mname], 40, n_spk)
@@ -196,21 +199,16 @@ def test_state_dict_round_trip_and_reference_keys():
             assert tuple(v.shape) == tuple(W[k].shape) and torch.equal(v, W[k].to(torch.float32)), k
         net2 = SynthesizerTrn(40, 513, 32, n_speakers=n_spk, **config.MODEL_CONFIGS[mname]).load_state_dict(out)
         assert torch.equal(net2._blob, net._blob)
-    from oracle import ref_import
-    if not ref_import.available():
-        return
-    import contextlib
-    import io
-    Ref, *_ = ref_import.import_reference()
-    with contextlib.redirect_stdout(io.StringIO()):
-        ref = Ref(40, 513, 32, n_speakers=3, **config.MODEL_CONFIGS["tiny"]).eval()
-    ref.dec.remove_weight_norm()
-    ref.flow.remove_weight_norm()
+    # the reference's load_state_dict(strict=False): no unexpected key, no shape mismatch, only training-side keys missing
+    ref = _ref_state_dict("tiny_rwn_40_3")
     cfg = config.make_config(config.MODEL_CONFIGS["tiny"], 40, 3)
     net = SynthesizerTrn(40, 513, 32, n_speakers=3, **config.MODEL_CONFIGS["tiny"]).load_state_dict(
         synth.make_state_dict(cfg, 5))
-    missing, unexpected = ref.load_state_dict(net.state_dict(), strict=False)
-    assert not unexpected
+    out = net.state_dict()
+    unexpected = [k for k in out if k not in ref]
+    assert not unexpected, unexpected
+    assert all(tuple(v.shape) == ref[k] for k, v in out.items()), [k for k, v in out.items() if tuple(v.shape) != ref[k]]
+    missing = [k for k in ref if k not in out]
     assert all(k.startswith(("enc_q.", "dp.post_", "dp.flows.1.")) for k in missing), missing
 
 
@@ -421,16 +419,11 @@ def test_is_onnx_is_a_constructor_argument_not_an_ignored_kwarg():
     assert net.cfg.is_onnx == 0 and "dec.stft.inverse_basis" not in net.state_dict()
     # a checkpoint saved from an is_onnx module carries the buffers: loading it must not trip on them
     net.load_state_dict(dict(sd, **{"dec.stft.inverse_basis": inv, "dec.stft.forward_basis": inv}))
-    from oracle import ref_import
-    if ref_import.available():
-        Ref, *_ = ref_import.import_reference()
-        import contextlib
-        import io
-        with contextlib.redirect_stdout(io.StringIO()):
-            ref = Ref(40, 513, 32, n_speakers=2, **dict(config.MODEL_CONFIGS["tiny_vocos"], is_onnx=True)).eval()
-        rsd = ref.state_dict()
-        net.set_is_onnx(True)
-        out = net.state_dict()
+    # the reference module's own two buffers (tiny_vocos, is_onnx, 40 symbols, 2 speakers)
+    net.set_is_onnx(True)
+    out = net.state_dict()
+    with np.load(REF_STATE_DICTS) as z:
         for k in ("dec.stft.forward_basis", "dec.stft.inverse_basis"):
-            assert tuple(rsd[k].shape) == tuple(out[k].shape)
-            assert float((rsd[k] - out[k]).abs().max()) < 1e-8, k
+            ref = torch.from_numpy(z["tiny_vocos_onnx_40_2_" + k.split(".")[-1]])
+            assert tuple(ref.shape) == tuple(out[k].shape)
+            assert float((ref - out[k]).abs().max()) < 1e-8, k
