@@ -17,7 +17,8 @@
  *     from the caller's workspace (wetts_workspace_bytes()).  Device memory is allocated by wetts_create()
  *     and by the two precision setters (wetts_set_decoder_precision / wetts_set_flow_precision), which build
  *     their 16-bit / uint8 weight copies when called, on the default stream, and return after it has drained
- *     (set-up calls, like create); wetts_dynamic_quant_conv1d and wetts_set_mrf_timing are validation / measurement
+ *     (set-up calls, like create), and by wetts_load_posterior_encoder (voice conversion, the same kind of set-up
+ *     call); wetts_dynamic_quant_conv1d and wetts_set_mrf_timing are validation / measurement
  *     aids and say so at their declarations.
  *   - return value: 0 = ok, negative = error (WETTS_E_*); wetts_last_error() gives the message
  *     of the calling thread's last failure.  Kernels never fall back to a CPU path.
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WETTS_ABI_VERSION 9
+#define WETTS_ABI_VERSION 10
 
 #define WETTS_OK 0
 #define WETTS_E_INVALID (-1)   /* bad argument / unsupported configuration */
@@ -137,6 +138,17 @@ int32_t wetts_blob_tensor_info(const wetts_config_t* cfg, int32_t index, char* n
                                size_t name_buf_len, int64_t* offset, int64_t* numel,
                                int64_t shape[4]);
 int64_t wetts_blob_numel(const wetts_config_t* cfg);
+
+/* The posterior encoder's tensors (`enc_q`, PosteriorEncoder(spec_channels, inter, hidden, 5, 1, 16, gin_channels),
+ * models.py:125-133, encoders.py:60-99) form a blob of their own, laid out like the main one (folded weight norm,
+ * reference keys enc_q.pre.*, enc_q.enc.in_layers.{i}.*, enc_q.enc.res_skip_layers.{i}.*, enc_q.enc.cond_layer.* when
+ * gin_channels > 0, enc_q.proj.*).  Only voice conversion needs them; the main blob does not change.  spec_channels is
+ * the checkpoint's n_fft / 2 + 1 (513 for every recipe: filter_length 1024). */
+int32_t wetts_posterior_blob_num_tensors(const wetts_config_t* cfg, int32_t spec_channels);
+int32_t wetts_posterior_blob_tensor_info(const wetts_config_t* cfg, int32_t spec_channels, int32_t index,
+                                         char* name_buf, size_t name_buf_len, int64_t* offset, int64_t* numel,
+                                         int64_t shape[4]);
+int64_t wetts_posterior_blob_numel(const wetts_config_t* cfg, int32_t spec_channels);
 
 /* ---- model lifetime ---------------------------------------------------------------------- */
 
@@ -317,6 +329,32 @@ int32_t wetts_dynamic_quant_conv1d(const float* x, const float* w, const float* 
  * cond_layer convs, the coupling and everything else stay f32.  BASELINE.json configs[2] ("bf16")
  * precision for the part of the step that dominates at B = 64.  The 16-bit weight copies are packed by this call. */
 int32_t wetts_set_flow_precision(const wetts_model_t* m, int32_t precision);
+
+/* ---- voice conversion (SynthesizerTrn.voice_conversion, models.py:369-376) ------------------------------------ */
+
+/* Set-up call (like the precision setters): copies the posterior blob (wetts_posterior_blob_tensor_info order, device
+ * pointer, may be freed after the call) into the model, packs the posterior encoder's convs and natural-order copies of
+ * the flow's `pre` convs for the forward direction, and returns after `stream` has drained.  A second call replaces
+ * the first; the caller has synchronised the streams that used the model. */
+int32_t wetts_load_posterior_encoder(wetts_model_t* m, int32_t spec_channels, const float* blob_dev, int64_t numel,
+                                     void* stream);
+
+/* Scratch of wetts_posterior_encoder and wetts_flow_forward for B utterances of Ty frames. */
+int64_t wetts_posterior_workspace_bytes(const wetts_model_t* m, int32_t B, int32_t Ty);
+
+/* PosteriorEncoder.forward (encoders.py:91-99), f32:
+ *   y [B, spec_channels, Ty] linear spectrogram, y_lengths [B] int64, g [B, gin] (may be NULL = g=None),
+ *   eps [B, inter, Ty] the caller's standard-normal draw (torch.randn_like, encoders.py:98);
+ *   z [B, inter, Ty] = (m + eps * exp(logs)) * y_mask; m_q / logs_q [B, inter, Ty] may be NULL; y_mask [B, Ty]. */
+int32_t wetts_posterior_encoder(const wetts_model_t* m, const float* y, const int64_t* y_lengths, const float* g,
+                                const float* eps, int32_t B, int32_t Ty, float* z, float* m_q, float* logs_q,
+                                float* y_mask, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ResidualCouplingTransformersBlock.forward(reverse=False) (flows.py:442-446) for every flow type wetts_flow_reverse
+ * supports; the log-determinant is not computed (voice_conversion discards it).  z, z_p [B, inter, Ty].  Honours
+ * wetts_set_flow_precision.  Needs wetts_load_posterior_encoder first. */
+int32_t wetts_flow_forward(const wetts_model_t* m, const float* z, const float* y_mask, const float* g, int32_t B,
+                           int32_t Ty, float* z_p, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* a15 monotonic_align.maximum_path (utils/monotonic_align.py:6-57).  Needs no model.
  *   neg_cent [B,Ty,Tx] float32 (not modified), t_ys / t_xs int32[B] (the mask sums the

@@ -1,0 +1,121 @@
+"""CPU tier of voice conversion: the posterior encoder's blob layout (held to the live reference's `enc_q.*` keys and
+shapes in tests/golden/reference_state_dicts.npz), its packing, the state_dict surface with and without `enc_q`, the
+untouched main blob, and the resources of the new kernels (no GPU needed)."""
+import json
+import os
+import shutil
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import util
+from wetts_amd import SynthesizerTrn, _lib, checkpoint, config, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_STATE_DICTS = os.path.join(util.GOLDEN, "reference_state_dicts.npz")
+SPEC = 513
+# (model, n_vocab, n_speakers) of the pinned reference state_dicts (make_golden.py:STATE_DICT_MODELS)
+PINNED = [("v1", 50, 1), ("v3", 50, 2), ("vocos", 50, 2), ("vits2_vocos_v1", 50, 1), ("tiny_preconv2_spk", 50, 3)]
+
+
+def _cfg(mname, n_vocab=40, n_spk=3):
+    return config.make_config(dict(config.MODEL_CONFIGS[mname]), n_vocab, n_spk)
+
+
+@pytest.mark.parametrize("mname,n_vocab,n_spk", PINNED)
+def test_posterior_layout_matches_reference_enc_q(mname, n_vocab, n_spk):
+    ref = json.loads(str(np.load(REF_STATE_DICTS)[f"sd_{mname}_{n_spk}"]))
+    want = {k: tuple(v) for k, v in ref.items() if k.startswith("enc_q.")}
+    assert len(want) == 70
+    got = {name: shape for name, _, _, shape in checkpoint.posterior_layout(_cfg(mname, n_vocab, n_spk), SPEC)}
+    assert got == want
+    lay = checkpoint.posterior_layout(_cfg(mname, n_vocab, n_spk), SPEC)
+    assert checkpoint.posterior_numel(_cfg(mname, n_vocab, n_spk), SPEC) >= lay[-1][1] + lay[-1][2]
+    assert all(off % 64 == 0 for _, off, _, _ in lay)  # 256-byte aligned, like the main blob
+
+
+def test_posterior_layout_rejects_bad_spec_channels():
+    assert _lib.load().wetts_posterior_blob_numel(_cfg("tiny"), 0) < 0
+    with pytest.raises(_lib.WettsError):
+        checkpoint.posterior_layout(_cfg("tiny"), -3)
+
+
+def test_pack_posterior_blob_round_trip_and_shape_check():
+    cfg = _cfg("tiny")
+    psd = synth.make_posterior_state_dict(cfg, SPEC, 5)
+    assert any(k.endswith(".weight_g") for k in psd)  # WN layers carry weight-norm pairs like a reference checkpoint
+    blob = checkpoint.pack_posterior_blob(cfg, SPEC, psd)
+    folded = checkpoint.fold_weight_norm(psd)
+    for name, off, numel, shape in checkpoint.posterior_layout(cfg, SPEC):
+        assert torch.equal(blob[off:off + numel].view(shape), folded[name].float())
+    bad = dict(psd)
+    bad["enc_q.proj.bias"] = torch.zeros(7)
+    with pytest.raises(ValueError):
+        checkpoint.pack_posterior_blob(cfg, SPEC, bad)
+    short = {k: v for k, v in psd.items() if not k.startswith("enc_q.proj.")}
+    with pytest.raises(KeyError):
+        checkpoint.pack_posterior_blob(cfg, SPEC, short)
+    assert not checkpoint.has_posterior(cfg, SPEC, short)
+    assert checkpoint.has_posterior(cfg, SPEC, psd)
+
+
+def _net(mname="tiny", n_spk=3):
+    return SynthesizerTrn(40, SPEC, 32, n_speakers=n_spk, **config.MODEL_CONFIGS[mname])
+
+
+def test_state_dict_with_enc_q_round_trips():
+    cfg = _cfg("tiny")
+    sd = synth.make_state_dict(cfg, 3)
+    psd = synth.make_posterior_state_dict(cfg, SPEC, 4)
+    net = _net().load_state_dict(dict(sd, **psd))
+    out = net.state_dict()
+    main = [name for name, _, _, _ in checkpoint.blob_layout(cfg)]
+    post = [name for name, _, _, _ in checkpoint.posterior_layout(cfg, SPEC)]
+    assert list(out) == main + post  # appended after today's keys, folded
+    again = _net().load_state_dict(out)
+    assert torch.equal(again._blob, net._blob)
+    assert torch.equal(again._post_blob, net._post_blob)
+    assert torch.equal(net._post_blob, checkpoint.pack_posterior_blob(cfg, SPEC, psd))
+
+
+def test_state_dict_without_enc_q_is_unchanged():
+    cfg = _cfg("tiny")
+    sd = synth.make_state_dict(cfg, 3)
+    net = _net().load_state_dict(sd)
+    assert net._post_blob is None
+    out = net.state_dict()
+    assert list(out) == [name for name, _, _, _ in checkpoint.blob_layout(cfg)]
+    blob = checkpoint.pack_blob(cfg, sd)
+    for name, off, numel, shape in checkpoint.blob_layout(cfg):
+        assert torch.equal(out[name], blob[off:off + numel].view(shape))
+    # a partial enc_q set is not a posterior encoder: it is ignored, as before
+    psd = synth.make_posterior_state_dict(cfg, SPEC, 4)
+    part = dict(sd, **{k: v for k, v in psd.items() if k.startswith("enc_q.pre.")})
+    assert _net().load_state_dict(part)._post_blob is None
+
+
+def test_voice_conversion_errors_before_any_device_work():
+    net = _net(n_spk=0).load_state_dict(synth.make_state_dict(_cfg("tiny", 40, 0), 1))
+    with pytest.raises(AttributeError):  # no emb_g, as in the reference
+        net.voice_conversion(torch.zeros(1, SPEC, 4), torch.tensor([4]), torch.tensor([0]), torch.tensor([0]))
+
+
+@pytest.mark.parametrize("name", util.INFER_CASES[:6] + ["aishell3_b4x128"])
+def test_main_blob_checksums_untouched(name):
+    util.case_model(util.load_case(name))  # asserts the stored blob checksum
+
+
+def test_new_kernels_have_no_scratch_and_full_occupancy():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    if not os.path.exists(kernel_resources.READELF) or shutil.which("c++filt") is None:
+        pytest.skip("needs llvm-readelf and c++filt")
+    table = kernel_resources.library_table(_lib.LIB_PATH)
+    names = ["wetts::coupling_fwd_flip_kernel", "wetts::mono_coupling_fwd_kernel", "wetts::seq_mask_kernel",
+             "wetts::posterior_sample_kernel"]
+    for k in names:
+        assert k in table, k
+        # element-wise kernels: no spills, and few enough registers for eight waves per SIMD
+        assert table[k]["ScratchSize"] == 0 and table[k]["VGPRs"] <= 64, (k, table[k])

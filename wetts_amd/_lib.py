@@ -22,7 +22,7 @@ class WettsError(RuntimeError):
     pass
 
 
-ABI_VERSION = 9  # WETTS_ABI_VERSION of include/wetts_hip.h this binding was written against
+ABI_VERSION = 10  # WETTS_ABI_VERSION of include/wetts_hip.h this binding was written against
 
 
 class Config(C.Structure):
@@ -98,6 +98,14 @@ SIGNATURES = {
     "wetts_length_regulate": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I64, _F, _I32, _I32, _I32,
                                      _P, _P, _P, _P, _P, _P, _P]),
     "wetts_flow_reverse": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
+    "wetts_posterior_blob_num_tensors": (_I32, [_CFG, _I32]),
+    "wetts_posterior_blob_tensor_info": (_I32, [_CFG, _I32, _I32, C.c_char_p, C.c_size_t, C.POINTER(_I64),
+                                                C.POINTER(_I64), C.POINTER(_I64 * 4)]),
+    "wetts_posterior_blob_numel": (_I64, [_CFG, _I32]),
+    "wetts_load_posterior_encoder": (_I32, [_P, _I32, _P, _I64, _P]),
+    "wetts_posterior_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_posterior_encoder": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
+    "wetts_flow_forward": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
     "wetts_hifigan": (_I32, [_P, _P, _I64, _I64, _P, _I64, _P, _I32, _I32, _P, _P, _I64, _P]),
     "wetts_hifigan_ragged_supported": (_I32, [_P]),
     "wetts_hifigan_ragged": (_I32, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _P]),

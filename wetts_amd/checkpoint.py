@@ -99,6 +99,58 @@ def pack_blob(cfg, state_dict, strict=True):
     return blob
 
 
+def posterior_layout(cfg, spec_channels):
+    """[(name, offset, numel, shape)] of the posterior encoder's own blob (`enc_q.*`, voice conversion), as the library
+    defines it (wetts_posterior_blob_tensor_info)."""
+    lib = _lib.load()
+    spec = int(spec_channels)
+    n = lib.wetts_posterior_blob_num_tensors(C.byref(cfg), spec)
+    if n < 0:
+        raise _lib.WettsError(f"invalid config: {_lib.last_error()}")
+    out = []
+    buf = C.create_string_buffer(256)
+    off, num, shape = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+    for i in range(n):
+        _lib.check(lib.wetts_posterior_blob_tensor_info(C.byref(cfg), spec, i, buf, 256, C.byref(off), C.byref(num),
+                                                        C.byref(shape)), "posterior_blob_tensor_info")
+        shp = tuple(int(s) for s in shape if s > 0)
+        out.append((buf.value.decode(), int(off.value), int(num.value), shp))
+    return out
+
+
+def posterior_numel(cfg, spec_channels):
+    n = _lib.load().wetts_posterior_blob_numel(C.byref(cfg), int(spec_channels))
+    if n < 0:
+        raise _lib.WettsError(f"invalid config: {_lib.last_error()}")
+    return int(n)
+
+
+def has_posterior(cfg, spec_channels, state_dict):
+    """True when `state_dict` carries every `enc_q.*` tensor of the layout (weight-norm pairs count as their weight)."""
+    sd = fold_weight_norm({k: v for k, v in state_dict.items() if k.startswith("enc_q.")})
+    return all(name in sd for name, _, _, _ in posterior_layout(cfg, spec_channels))
+
+
+def pack_posterior_blob(cfg, spec_channels, state_dict):
+    """Natural-layout float32 CPU blob of the posterior encoder (`enc_q.*`, weight norm folded) from a reference-keyed
+    state_dict.  Every tensor must be present (there is no init value to fall back to) and have its layout shape."""
+    sd = fold_weight_norm({k: v for k, v in state_dict.items() if k.startswith("enc_q.")})
+    blob = torch.zeros(posterior_numel(cfg, spec_channels), dtype=torch.float32)
+    missing = []
+    for name, off, numel, shape in posterior_layout(cfg, spec_channels):
+        t = sd.get(name)
+        if t is None:
+            missing.append(name)
+            continue
+        t = t.detach().to(torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != expected {shape}")
+        blob[off:off + numel] = t.reshape(-1)
+    if missing:
+        raise KeyError(f"{len(missing)} posterior encoder tensors missing from checkpoint: {missing}")
+    return blob
+
+
 def load_state_dict_file(checkpoint_path):
     """Reads `G_*.pth` as saved by task.save_checkpoint (task.py:59-76): {"model": state_dict,
     "iteration", "optimizer", "learning_rate"}; a bare state_dict is accepted too."""

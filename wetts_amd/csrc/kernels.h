@@ -135,6 +135,18 @@ int32_t k_mono_split(const float* x, const float* mask, int B, int C, int T, flo
                      hipStream_t s);
 int32_t k_mono_coupling(const float* x, const float* m, const float* mask, int B, int C, int T, float sc, float* out,
                         hipStream_t s);
+// forward direction of the flow (voice conversion, flows.py:442-446), mean-only couplings (logs = 0):
+// ResidualCouplingLayer then Flip, out = flip(cat(x0, m + x1 * mask)) (flows.py:505-509, :70-74, :159-163)
+int32_t k_coupling_fwd_flip(const float* x, const float* m, const float* mask, int B, int C, int T, float* out,
+                            hipStream_t s);
+// MonoTransformerFlowLayer forward: y = cat(x0, m + x1 * mask), out = residual ? x + y : y (flows.py:275-286,312-318)
+int32_t k_mono_coupling_fwd(const float* x, const float* m, const float* mask, int B, int C, int T, int residual,
+                            float* out, hipStream_t s);
+// PosteriorEncoder (encoders.py:91-99): sequence_mask into [B][Tp] rows (+ the caller's [B][T_in] copy, may be null),
+// and the sampling z = (m + eps * exp(logs)) * mask from stats [B][2C][Tp] into [B][C][T] (m_out / logs_out may be null)
+int32_t k_seq_mask(const int64_t* lengths, int B, int T_in, int Tp, float* mask, float* mask_out, hipStream_t s);
+int32_t k_posterior_sample(const float* stats, const float* eps, const float* mask, int B, int C, int T, int Tp,
+                           float* z, float* m_out, float* logs_out, hipStream_t s);
 // rows re-strided: dst[r][c] = c < cols_src ? src[r][c] : 0, c < cols_dst
 int32_t k_copy_rows(const float* src, int64_t src_stride, int cols_src, float* dst, int64_t dst_stride, int cols_dst,
                     int64_t rows, hipStream_t s);

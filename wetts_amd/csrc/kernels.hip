@@ -1179,6 +1179,107 @@ int32_t k_mono_coupling(const float* x, const float* m, const float* mask, int B
   return WETTS_OK;
 }
 
+// ---- forward direction of the flow (voice conversion, flows.py:442-446) ----------------------------------------------
+// ResidualCouplingLayer.forward(reverse=False) with mean_only (logs = 0, flows.py:505-509), then Flip:
+//   y = cat(x0, m + x1 * mask);  out = flip(y, channels)  ->  out[c] = y[C-1-c]
+__global__ void coupling_fwd_flip_kernel(const float* __restrict__ x, const float* __restrict__ m,
+                                         const float* __restrict__ mask, int B, int C, int T, float* __restrict__ out) {
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)B * C * T) return;
+  const int t = (int)(idx % T);
+  const int c = (int)((idx / T) % C);
+  const int b = (int)(idx / ((int64_t)T * C));
+  const int half = C / 2, src = C - 1 - c;
+  float v = x[((int64_t)b * C + src) * T + t];
+  if (src >= half) v = m[((int64_t)b * half + (src - half)) * T + t] + v * mask[(int64_t)b * T + t];
+  out[idx] = v;
+}
+
+int32_t k_coupling_fwd_flip(const float* x, const float* m, const float* mask, int B, int C, int T, float* out,
+                            hipStream_t s) {
+  int64_t n = (int64_t)B * C * T;
+  if (n == 0) return WETTS_OK;
+  hipLaunchKernelGGL(coupling_fwd_flip_kernel, grid1d(n, 256), dim3(256), 0, s, x, m, mask, B, C, T, out);
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
+// MonoTransformerFlowLayer.forward(reverse=False), mean_only (flows.py:275-286 residual, :312-318 inter):
+//   y = cat(x0, m + x1 * mask);  out = residual ? x + y : y   (residual: x0 + x0 and x1 + (m + x1 * mask))
+__global__ void mono_coupling_fwd_kernel(const float* __restrict__ x, const float* __restrict__ m,
+                                         const float* __restrict__ mask, int B, int C, int T, int residual,
+                                         float* __restrict__ out) {
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)B * C * T) return;
+  const int t = (int)(idx % T);
+  const int c = (int)((idx / T) % C);
+  const int b = (int)(idx / ((int64_t)T * C));
+  const int half = C / 2;
+  const float xv = x[idx];
+  float y = xv;
+  if (c >= half) y = m[((int64_t)b * half + (c - half)) * T + t] + xv * mask[(int64_t)b * T + t];
+  out[idx] = residual ? xv + y : y;
+}
+
+int32_t k_mono_coupling_fwd(const float* x, const float* m, const float* mask, int B, int C, int T, int residual,
+                            float* out, hipStream_t s) {
+  int64_t n = (int64_t)B * C * T;
+  if (n == 0) return WETTS_OK;
+  hipLaunchKernelGGL(mono_coupling_fwd_kernel, grid1d(n, 256), dim3(256), 0, s, x, m, mask, B, C, T, residual, out);
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
+// ---- PosteriorEncoder (encoders.py:91-99) -------------------------------------------------------------------------
+// x_mask = sequence_mask(lengths, T_in): mask [B][Tp] (columns T_in .. Tp-1 are 0, the padded rows of the flow
+// convention) and, if non-null, the caller's y_mask [B][T_in]
+__global__ void seq_mask_kernel(const int64_t* __restrict__ lengths, int B, int T_in, int Tp, float* __restrict__ mask,
+                                float* __restrict__ mask_out) {
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)B * Tp) return;
+  const int t = (int)(idx % Tp);
+  const int b = (int)(idx / Tp);
+  const float v = (t < T_in && (int64_t)t < lengths[b]) ? 1.f : 0.f;
+  mask[idx] = v;
+  if (mask_out && t < T_in) mask_out[(int64_t)b * T_in + t] = v;
+}
+
+int32_t k_seq_mask(const int64_t* lengths, int B, int T_in, int Tp, float* mask, float* mask_out, hipStream_t s) {
+  int64_t n = (int64_t)B * Tp;
+  if (n == 0) return WETTS_OK;
+  hipLaunchKernelGGL(seq_mask_kernel, grid1d(n, 256), dim3(256), 0, s, lengths, B, T_in, Tp, mask, mask_out);
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
+// stats [B][2C][Tp] (= proj(x) * mask) -> m, logs = split(stats);  z = (m + eps * exp(logs)) * mask, written with the
+// caller's row length T (<= Tp); eps [B][C][T] is the caller's standard-normal draw (torch.randn_like, encoders.py:98).
+// m_out / logs_out may be null.
+__global__ void posterior_sample_kernel(const float* __restrict__ stats, const float* __restrict__ eps,
+                                        const float* __restrict__ mask, int B, int C, int T, int Tp,
+                                        float* __restrict__ z, float* __restrict__ m_out, float* __restrict__ logs_out) {
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)B * C * T) return;
+  const int t = (int)(idx % T);
+  const int c = (int)((idx / T) % C);
+  const int b = (int)(idx / ((int64_t)T * C));
+  const float m = stats[((int64_t)b * 2 * C + c) * Tp + t];
+  const float ls = stats[((int64_t)b * 2 * C + C + c) * Tp + t];
+  z[idx] = (m + eps[idx] * expf(ls)) * mask[(int64_t)b * Tp + t];
+  if (m_out) m_out[idx] = m;
+  if (logs_out) logs_out[idx] = ls;
+}
+
+int32_t k_posterior_sample(const float* stats, const float* eps, const float* mask, int B, int C, int T, int Tp,
+                           float* z, float* m_out, float* logs_out, hipStream_t s) {
+  int64_t n = (int64_t)B * C * T;
+  if (n == 0) return WETTS_OK;
+  hipLaunchKernelGGL(posterior_sample_kernel, grid1d(n, 256), dim3(256), 0, s, stats, eps, mask, B, C, T, Tp, z,
+                     m_out, logs_out);
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
 // dst[r][c] = c < cols_src ? src[r][c] : 0 for c < cols_dst: rows re-strided (padded to a multiple of 4 columns
 // on the way in, trimmed on the way out)
 __global__ void copy_rows_kernel(const float* __restrict__ src, int64_t src_stride, int cols_src,

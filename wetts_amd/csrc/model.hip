@@ -330,6 +330,35 @@ static void build_layout(const wetts_config_t* c, Layout& L) {
   }
 }
 
+// PosteriorEncoder(spec_channels, inter, hidden, 5, 1, 16, gin_channels) (models.py:125-133, encoders.py:60-99): the
+// tensors of `enc_q`, held in a blob of their own (wetts_load_posterior_encoder) so the main blob stays as it is
+constexpr int kPostLayers = 16, kPostKernel = 5;
+
+static void build_posterior_layout(const wetts_config_t* c, int spec, Layout& L) {
+  const int H = c->hidden_channels, I = c->inter_channels;
+  L.add("enc_q.pre.weight", H, spec, 1);
+  L.add("enc_q.pre.bias", H);
+  for (int i = 0; i < kPostLayers; ++i) {
+    L.add(S("enc_q.enc.in_layers.%d.weight", i), 2 * H, H, kPostKernel);
+    L.add(S("enc_q.enc.in_layers.%d.bias", i), 2 * H);
+    const int rs = (i < kPostLayers - 1) ? 2 * H : H;
+    L.add(S("enc_q.enc.res_skip_layers.%d.weight", i), rs, H, 1);
+    L.add(S("enc_q.enc.res_skip_layers.%d.bias", i), rs);
+  }
+  if (c->gin_channels > 0) {  // WN builds cond_layer whenever gin_channels != 0 (modules.py:35-36)
+    L.add("enc_q.enc.cond_layer.weight", 2 * H * kPostLayers, c->gin_channels, 1);
+    L.add("enc_q.enc.cond_layer.bias", 2 * H * kPostLayers);
+  }
+  L.add("enc_q.proj.weight", 2 * I, H, 1);
+  L.add("enc_q.proj.bias", 2 * I);
+}
+
+static int validate_posterior(const wetts_config_t* c, int spec) {
+  WETTS_TRY(validate_config(c));
+  WETTS_REQUIRE(spec >= 1 && spec <= 65536, "bad spec_channels %d", spec);
+  return WETTS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------------------------
@@ -484,6 +513,17 @@ struct wetts_model {
   hipStream_t aux_stream[WETTS_MAX_RB_KERNELS] = {};
   hipEvent_t ev_fork = nullptr, ev_chain[WETTS_MAX_RB_KERNELS] = {};
   bool fork_ok = false;  // every handle above exists (else: the serial grouped schedule)
+
+  // posterior encoder + forward flow (voice conversion), built by wetts_load_posterior_encoder: enc_q's own blob, its
+  // packed convs, and natural-order copies of the flow's `pre` for the forward direction (the reverse packs plain /
+  // pre_conv2 `pre` with the Flip folded into its input order)
+  int spec_channels = 0;
+  bool post_loaded = false;
+  Layout post_layout;
+  float* post_blob = nullptr;
+  PackedConv pe_pre, pe_proj;
+  std::vector<PackedConv> pe_in, pe_rs, fwd_pre;
+  const float *pe_cond_w = nullptr, *pe_cond_b = nullptr;
 
   const float* T(const std::string& name) const {
     auto it = layout.index.find(name);
@@ -868,6 +908,29 @@ static int64_t ws_decoder(const wetts_config_t* c, int B, int L) {
   return f32need > u8need ? f32need : u8need;
 }
 
+static void free_posterior(wetts_model* m) {
+  free_packed(&m->pe_pre);
+  free_packed(&m->pe_proj);
+  for (auto* v : {&m->pe_in, &m->pe_rs, &m->fwd_pre})
+    for (PackedConv& pc : *v) free_packed(&pc);
+  m->pe_in.clear();
+  m->pe_rs.clear();
+  m->fwd_pre.clear();
+  if (m->post_blob) (void)hipFree(m->post_blob);
+  m->post_blob = nullptr;
+  m->pe_cond_w = m->pe_cond_b = nullptr;
+  m->post_layout = Layout();
+  m->post_loaded = false;
+}
+
+// scratch of wetts_posterior_encoder: mask rows, h, the f32 WN buffers, cond_layer output, stats
+static int64_t ws_posterior(const wetts_config_t* c, int B, int Ty_) {
+  const int64_t H = c->hidden_channels, I = c->inter_channels;
+  const int64_t Ty = ((int64_t)Ty_ + 3) & ~3ll;
+  return A256(B * Ty) + 3 * A256(B * H * Ty) + 2 * A256(B * 2 * H * Ty) + A256(B * 2 * H * kPostLayers) +
+         A256(B * 2 * I * Ty);
+}
+
 }  // namespace wetts
 
 // =============================================================================================
@@ -907,6 +970,37 @@ int64_t wetts_blob_numel(const wetts_config_t* cfg) {
   if (validate_config(cfg) != WETTS_OK) return WETTS_E_INVALID;
   Layout L;
   build_layout(cfg, L);
+  return L.total;
+}
+
+int32_t wetts_posterior_blob_num_tensors(const wetts_config_t* cfg, int32_t spec_channels) {
+  if (validate_posterior(cfg, spec_channels) != WETTS_OK) return WETTS_E_INVALID;
+  Layout L;
+  build_posterior_layout(cfg, spec_channels, L);
+  return (int32_t)L.specs.size();
+}
+
+int32_t wetts_posterior_blob_tensor_info(const wetts_config_t* cfg, int32_t spec_channels, int32_t index,
+                                         char* name_buf, size_t name_buf_len, int64_t* offset, int64_t* numel,
+                                         int64_t shape[4]) {
+  WETTS_TRY(validate_posterior(cfg, spec_channels));
+  Layout L;
+  build_posterior_layout(cfg, spec_channels, L);
+  WETTS_REQUIRE(index >= 0 && index < (int32_t)L.specs.size(), "tensor index %d out of range", index);
+  const TensorSpec& t = L.specs[index];
+  WETTS_REQUIRE(name_buf && name_buf_len > t.name.size(), "name buffer too small");
+  strcpy(name_buf, t.name.c_str());
+  if (offset) *offset = t.offset;
+  if (numel) *numel = t.numel;
+  if (shape)
+    for (int i = 0; i < 4; ++i) shape[i] = t.shape[i];
+  return WETTS_OK;
+}
+
+int64_t wetts_posterior_blob_numel(const wetts_config_t* cfg, int32_t spec_channels) {
+  if (validate_posterior(cfg, spec_channels) != WETTS_OK) return WETTS_E_INVALID;
+  Layout L;
+  build_posterior_layout(cfg, spec_channels, L);
   return L.total;
 }
 
@@ -1006,6 +1100,7 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
 
 void wetts_destroy(wetts_model_t* m) {
   if (!m) return;
+  free_posterior(m);
   for (PackedConv* pc : m->all_packed) free_packed(pc);
   for (auto& pc : m->b_ups) free_packed_bf16(&pc);
   for (auto& v : m->b_c1) for (auto& pc : v) free_packed_bf16(&pc);
@@ -1061,6 +1156,12 @@ int64_t wetts_workspace_bytes(const wetts_model_t* m, int32_t B, int32_t Tx, int
     if (d > need) need = d;
   }
   return need + 4096;
+}
+
+int64_t wetts_posterior_workspace_bytes(const wetts_model_t* m, int32_t B, int32_t Ty) {
+  if (!m || B < 0 || Ty < 0) return WETTS_E_INVALID;
+  const int64_t a = ws_posterior(&m->cfg, B, Ty), f = ws_flow(&m->cfg, B, Ty);
+  return (a > f ? a : f) + 4096;
 }
 
 int32_t wetts_speaker_embedding(const wetts_model_t* m, const int64_t* sid, int32_t B,
@@ -1435,6 +1536,148 @@ static int32_t pack_flow_bf16(const wetts_model* m, hipStream_t s) {
   m->flow_packed_prec = want;
   return WETTS_OK;
 }
+// WN.forward (modules.py:60-87) on h [B,H,Ty] (masked, rows of Ty = a multiple of 4 frames), leaving the
+// un-masked skip sum in w.skip [B,H,Ty] (its consumer masks it).  h is updated in place.  gl: the cond_layer output
+// [B][2H * NL] (speaker conditioning) or null.  wn16 = 0: f32 convs (in_layers with the gate in their epilogue);
+// 1 / 2: the bf16 / f16 copies w_in16 / w_rs16 (wn16.hip).  Shared by the flow (both directions) and the posterior encoder.
+struct WnScratch {
+  float *acts, *skip, *xin, *rs, *skip_cl;
+  unsigned short *h16, *acts16, *xin16, *rs16;
+};
+
+static int32_t run_wn(const wetts_model* m, const std::vector<PackedConv>& in_layers,
+                      const std::vector<PackedConv>& res_skip, const std::vector<PackedConvB>* w_in16,
+                      const std::vector<PackedConvB>* w_rs16, int wn16, float* h, const float* y_mask, const float* gl,
+                      int B, int H, int Ty, const WnScratch& w, hipStream_t s) {
+  const int NL = (int)in_layers.size();
+  float *acts = w.acts, *skip = w.skip, *xin = w.xin, *rs = w.rs, *skip_cl = w.skip_cl;
+  unsigned short *h16 = w.h16, *acts16 = w.acts16, *xin16 = w.xin16, *rs16 = w.rs16;
+  if (wn16) {
+    // WN at 16 bit (wn16.hip): channel-last activations, f32 accumulation, the skip sum in f32
+    const int f16 = wn16 == 2 ? 1 : 0;
+    const int64_t rows = (int64_t)B * Ty;
+    WETTS_TRY(k_cf32_to_cl16(h, h16, B, H, Ty, f16, s));
+    for (int i = 0; i < NL; ++i) {
+      const bool last = (i == NL - 1);
+      ConvBParams p1;
+      memset(&p1, 0, sizeof(p1));
+      p1.x = h16; p1.x_bs = (int64_t)H * Ty; p1.Cin = H; p1.Tin = Ty; p1.in_act = IN_NONE;
+      p1.out = xin16; p1.o_bs = (int64_t)2 * H * Ty; p1.cout = 2 * H; p1.Tout = Ty;
+      p1.out_div = 1.f; p1.B = B;
+      if (gl) {
+        p1.bias_b = gl + (int64_t)i * 2 * H;
+        p1.bias_b_stride = (int64_t)2 * H * NL;
+      }
+      const bool fusedwn = wn16_fused(H);
+      if (fusedwn) {  // gate in the epilogue: acts16 written directly
+        p1.epi_mode = 1;
+        p1.wn_H = H;
+        p1.out = acts16;
+        p1.o_bs = (int64_t)H * Ty;
+      }
+      WETTS_TRY(launch_conv_bf16((*w_in16)[i], p1, s));
+      if (!fusedwn) WETTS_TRY(k_gate_cl16(xin16, acts16, rows, H, f16, s));
+      const int RC = last ? H : 2 * H;
+      ConvBParams p2;
+      memset(&p2, 0, sizeof(p2));
+      p2.x = acts16; p2.x_bs = (int64_t)H * Ty; p2.Cin = H; p2.Tin = Ty; p2.in_act = IN_NONE;
+      p2.out = rs16; p2.o_bs = (int64_t)RC * Ty; p2.cout = RC; p2.Tout = Ty;
+      p2.out_div = 1.f; p2.B = B;
+      if (fusedwn) {  // h / skip update in the epilogue: rs16 is never written
+        p2.epi_mode = 2;
+        p2.wn_H = H;
+        p2.wn_h = h16;
+        p2.wn_skip = skip_cl;
+        p2.wn_mask = y_mask;
+        p2.wn_last = last ? 1 : 0;
+        p2.wn_first = i == 0 ? 1 : 0;
+      }
+      WETTS_TRY(launch_conv_bf16((*w_rs16)[i], p2, s));
+      if (!fusedwn)
+        WETTS_TRY(k_wn_update_cl16(rs16, h16, skip_cl, y_mask, last ? 1 : 0, i == 0 ? 1 : 0, rows, H, f16, s));
+    }
+    WETTS_TRY(k_cl32_to_cf32(skip_cl, skip, B, H, Ty, s));
+  } else
+  for (int i = 0; i < NL; ++i) {
+    {
+      // acts = tanh(a[:H]) * sigmoid(a[H:]),  a = in_layer(h) (+ g_l)  (modules.py:71-78, commons.py:98-105): the gate
+      // runs in the conv's epilogue (rows packed interleaved), x_in is never written
+      const bool gate = in_layers[i].gate_H > 0;
+      ConvParams p = conv_io(h, H, Ty, gate ? acts : xin, gate ? H : 2 * H, B);
+      if (gate) p.out_act = OUT_GATE;
+      if (gl) {
+        p.bias_b = gl + (int64_t)i * 2 * H;
+        p.bias_b_stride = (int64_t)2 * H * NL;
+      }
+      WETTS_TRY(launch_conv(in_layers[i], p, s));
+      if (!gate) WETTS_TRY(k_gate(xin, B, H, Ty, acts, s));
+    }
+    const bool last = (i == NL - 1);
+    ConvParams p2 = conv_io(acts, H, Ty, rs, last ? H : 2 * H, B);
+    // residual / skip update in the conv's epilogue (rs never exists, one launch less per layer) where launches are
+    // the cost: the calls the small-launch conv kernel takes.  Big batches keep the specialised conv epilogue and
+    // the separate update -- the generic epilogue costs them 0.2 % of the headline step (profiles/r03_wn_fuse_ab.txt)
+    // ... and launches the LDS-DMA GEMM takes (gemm_pw.hip: h / skip rows come in through the accumulator init, so
+    // its epilogue stays a plain store; rows are 16-byte aligned, see the top of wetts_flow_reverse)
+    const bool fuse_upd = m->wn_fuse == 2 ||
+                          (m->wn_fuse == 1 && ((int64_t)cdiv(last ? H : 2 * H, 64) * cdiv(Ty, 64) * B <= m->small_max_tiles ||
+                                               (H % 32) == 0));
+    if (fuse_upd) {
+      p2.wn_h = h;
+      p2.wn_skip = skip;
+      p2.wn_mask = y_mask;
+      p2.wn_mask_stride = Ty;
+      p2.wn_H = H;
+      p2.wn_last = last ? 1 : 0;
+      p2.wn_first = i == 0 ? 1 : 0;
+    }
+    WETTS_TRY(launch_conv(res_skip[i], p2, s));
+    if (!fuse_upd) WETTS_TRY(k_wn_update(rs, h, skip, y_mask, last ? 1 : 0, i == 0 ? 1 : 0, B, H, Ty, s));
+  }
+  return WETTS_OK;
+}
+
+// The flow's scratch (both directions): padded copies of the input and mask (when Ty_in is not a multiple of 4), the
+// two ping-pong tensors, the WN buffers (f32 and 16-bit), and the transformer flows' encoder scratch.
+struct FlowScratch {
+  float *zp_pad, *mask_pad, *xa, *xb, *h, *mm, *gl;
+  WnScratch wn;
+  float *tx0 = nullptr, *txm = nullptr, *tq = nullptr, *tk = nullptr, *tv = nullptr, *tatt = nullptr, *ty = nullptr,
+        *thid = nullptr, *txb = nullptr, *tsc = nullptr;
+};
+
+static bool take_flow_scratch(const wetts_model* m, int B, int Ty, bool repad, Bump& ws, FlowScratch& f) {
+  const wetts_config_t* c = &m->cfg;
+  const int H = c->hidden_channels, I = c->inter_channels, NL = c->flow_wn_layers;
+  f.zp_pad = ws.take<float>(repad ? (int64_t)B * I * Ty : 0);
+  f.mask_pad = ws.take<float>(repad ? (int64_t)B * Ty : 0);
+  f.xa = ws.take<float>((int64_t)B * I * Ty);
+  f.xb = ws.take<float>((int64_t)B * I * Ty);
+  f.h = ws.take<float>((int64_t)B * H * Ty);
+  f.wn.acts = ws.take<float>((int64_t)B * H * Ty);
+  f.wn.skip = ws.take<float>((int64_t)B * H * Ty);
+  f.wn.xin = ws.take<float>((int64_t)B * 2 * H * Ty);
+  f.wn.rs = ws.take<float>((int64_t)B * 2 * H * Ty);
+  f.mm = ws.take<float>((int64_t)B * (I / 2) * Ty);
+  f.gl = ws.take<float>((int64_t)B * 2 * H * NL);
+  f.wn.h16 = ws.take<unsigned short>((int64_t)B * H * Ty);
+  f.wn.acts16 = ws.take<unsigned short>((int64_t)B * H * Ty);
+  f.wn.xin16 = ws.take<unsigned short>((int64_t)B * 2 * H * Ty);
+  f.wn.rs16 = ws.take<unsigned short>((int64_t)B * 2 * H * Ty);
+  f.wn.skip_cl = ws.take<float>((int64_t)B * H * Ty);
+  if (c->transformer_flows != 0) {
+    // encoder width: x0 (I/2 channels) for pre_conv / mono layers, the hidden h for pre_conv2
+    const int64_t nh2 = (int64_t)B * (half_enc_flows(c) ? I / 2 : H) * Ty;
+    f.tx0 = ws.take<float>(nh2); f.txm = ws.take<float>(nh2); f.tq = ws.take<float>(nh2);
+    f.tk = ws.take<float>(nh2); f.tv = ws.take<float>(nh2); f.tatt = ws.take<float>(nh2);
+    f.ty = ws.take<float>(nh2); f.thid = ws.take<float>(nh2); f.txb = ws.take<float>(nh2);
+    const int He = half_enc_flows(c) ? I / 2 : H;
+    f.tsc = ws.take<float>(attn_score_elems(half_enc_flows(c) ? -1 : 4, He / 2, B, 2, Ty) + nh2 +
+                           (int64_t)B * 2 * 9 * Ty);  // scores (three-kernel path only) + vT + rel table
+  }
+  return ws.ok;
+}
+
 }  // namespace wetts
 
 int32_t wetts_set_flow_precision(const wetts_model_t* m, int32_t precision) {
@@ -1466,40 +1709,18 @@ int32_t wetts_flow_reverse(const wetts_model_t* m, const float* z_p_in, const fl
   // multiple of 4, z_p and the mask are copied into padded rows first and z is copied out at the end.
   const int Ty = (Ty_in + 3) & ~3;
   const bool repad = Ty != Ty_in;
-  float* zp_pad = ws.take<float>(repad ? (int64_t)B * I * Ty : 0);
-  float* mask_pad = ws.take<float>(repad ? (int64_t)B * Ty : 0);
-  float* xa = ws.take<float>((int64_t)B * I * Ty);
-  float* xb = ws.take<float>((int64_t)B * I * Ty);
-  float* h = ws.take<float>((int64_t)B * H * Ty);
-  float* acts = ws.take<float>((int64_t)B * H * Ty);
-  float* skip = ws.take<float>((int64_t)B * H * Ty);
-  float* xin = ws.take<float>((int64_t)B * 2 * H * Ty);
-  float* rs = ws.take<float>((int64_t)B * 2 * H * Ty);
-  float* mm = ws.take<float>((int64_t)B * (I / 2) * Ty);
-  float* gl = ws.take<float>((int64_t)B * 2 * H * NL);
-  unsigned short* h16 = ws.take<unsigned short>((int64_t)B * H * Ty);
-  unsigned short* acts16 = ws.take<unsigned short>((int64_t)B * H * Ty);
-  unsigned short* xin16 = ws.take<unsigned short>((int64_t)B * 2 * H * Ty);
-  unsigned short* rs16 = ws.take<unsigned short>((int64_t)B * 2 * H * Ty);
-  float* skip_cl = ws.take<float>((int64_t)B * H * Ty);
-  const int wn16 = m->flow_precision;  // 0: f32 WN, 1 / 2: bf16 / f16 convs and activations
-  if (wn16) WETTS_TRY(pack_flow_bf16(m, s));
-  float *tx0 = nullptr, *txm = nullptr, *tq = nullptr, *tk = nullptr, *tv = nullptr,
-        *tatt = nullptr, *ty = nullptr, *thid = nullptr, *txb = nullptr, *tsc = nullptr;
-  if (c->transformer_flows != 0) {
-    // encoder width: x0 (I/2 channels) for pre_conv, the hidden h for pre_conv2
-    const int64_t nh2 = (int64_t)B * (half_enc_flows(c) ? I / 2 : H) * Ty;
-    tx0 = ws.take<float>(nh2); txm = ws.take<float>(nh2); tq = ws.take<float>(nh2);
-    tk = ws.take<float>(nh2); tv = ws.take<float>(nh2); tatt = ws.take<float>(nh2);
-    ty = ws.take<float>(nh2); thid = ws.take<float>(nh2); txb = ws.take<float>(nh2);
-    const int He = half_enc_flows(c) ? I / 2 : H;
-    tsc = ws.take<float>(attn_score_elems(half_enc_flows(c) ? -1 : 4, He / 2, B, 2, Ty) + nh2 +
-                         (int64_t)B * 2 * 9 * Ty);  // scores (three-kernel path only) + vT + rel table
-  }
-  if (!ws.ok) {
+  FlowScratch fs;
+  if (!take_flow_scratch(m, B, Ty, repad, ws, fs)) {
     set_error("flow_reverse: workspace too small");
     return WETTS_E_WORKSPACE;
   }
+  float *zp_pad = fs.zp_pad, *mask_pad = fs.mask_pad, *xa = fs.xa, *xb = fs.xb, *h = fs.h, *skip = fs.wn.skip,
+        *mm = fs.mm, *gl = fs.gl;
+  float *tx0 = fs.tx0, *txm = fs.txm, *tq = fs.tq, *tk = fs.tk, *tv = fs.tv, *tatt = fs.tatt, *ty = fs.ty,
+        *thid = fs.thid, *txb = fs.txb, *tsc = fs.tsc;
+  const WnScratch& wsc = fs.wn;
+  const int wn16 = m->flow_precision;  // 0: f32 WN, 1 / 2: bf16 / f16 convs and activations
+  if (wn16) WETTS_TRY(pack_flow_bf16(m, s));
   const float* z_p = z_p_in;
   const float* y_mask = y_mask_in;
   float* z_out = z_out_user;
@@ -1565,88 +1786,8 @@ int32_t wetts_flow_reverse(const wetts_model_t* m, const float* z_p_in, const fl
     const bool use_g = has_g(c) && g;
     if (use_g)
       WETTS_TRY(k_cond_linear(g, fw.cond_w, fw.cond_b, B, 2 * H * NL, c->gin_channels, gl, s));
-    if (wn16) {
-      // WN at 16 bit (wn16.hip): channel-last activations, f32 accumulation, the skip sum in f32
-      const int f16 = wn16 == 2 ? 1 : 0;
-      const int64_t rows = (int64_t)B * Ty;
-      WETTS_TRY(k_cf32_to_cl16(h, h16, B, H, Ty, f16, s));
-      for (int i = 0; i < NL; ++i) {
-        const bool last = (i == NL - 1);
-        ConvBParams p1;
-        memset(&p1, 0, sizeof(p1));
-        p1.x = h16; p1.x_bs = (int64_t)H * Ty; p1.Cin = H; p1.Tin = Ty; p1.in_act = IN_NONE;
-        p1.out = xin16; p1.o_bs = (int64_t)2 * H * Ty; p1.cout = 2 * H; p1.Tout = Ty;
-        p1.out_div = 1.f; p1.B = B;
-        if (use_g) {
-          p1.bias_b = gl + (int64_t)i * 2 * H;
-          p1.bias_b_stride = (int64_t)2 * H * NL;
-        }
-        const bool fusedwn = wn16_fused(H);
-        if (fusedwn) {  // gate in the epilogue: acts16 written directly
-          p1.epi_mode = 1;
-          p1.wn_H = H;
-          p1.out = acts16;
-          p1.o_bs = (int64_t)H * Ty;
-        }
-        WETTS_TRY(launch_conv_bf16(m->b_wn_in[f][i], p1, s));
-        if (!fusedwn) WETTS_TRY(k_gate_cl16(xin16, acts16, rows, H, f16, s));
-        const int RC = last ? H : 2 * H;
-        ConvBParams p2;
-        memset(&p2, 0, sizeof(p2));
-        p2.x = acts16; p2.x_bs = (int64_t)H * Ty; p2.Cin = H; p2.Tin = Ty; p2.in_act = IN_NONE;
-        p2.out = rs16; p2.o_bs = (int64_t)RC * Ty; p2.cout = RC; p2.Tout = Ty;
-        p2.out_div = 1.f; p2.B = B;
-        if (fusedwn) {  // h / skip update in the epilogue: rs16 is never written
-          p2.epi_mode = 2;
-          p2.wn_H = H;
-          p2.wn_h = h16;
-          p2.wn_skip = skip_cl;
-          p2.wn_mask = y_mask;
-          p2.wn_last = last ? 1 : 0;
-          p2.wn_first = i == 0 ? 1 : 0;
-        }
-        WETTS_TRY(launch_conv_bf16(m->b_wn_rs[f][i], p2, s));
-        if (!fusedwn)
-          WETTS_TRY(k_wn_update_cl16(rs16, h16, skip_cl, y_mask, last ? 1 : 0, i == 0 ? 1 : 0, rows, H, f16, s));
-      }
-      WETTS_TRY(k_cl32_to_cf32(skip_cl, skip, B, H, Ty, s));
-    } else
-    for (int i = 0; i < NL; ++i) {
-      {
-        // acts = tanh(a[:H]) * sigmoid(a[H:]),  a = in_layer(h) (+ g_l)  (modules.py:71-78, commons.py:98-105): the gate
-        // runs in the conv's epilogue (rows packed interleaved), x_in is never written
-        const bool gate = fw.in_layers[i].gate_H > 0;
-        ConvParams p = conv_io(h, H, Ty, gate ? acts : xin, gate ? H : 2 * H, B);
-        if (gate) p.out_act = OUT_GATE;
-        if (use_g) {
-          p.bias_b = gl + (int64_t)i * 2 * H;
-          p.bias_b_stride = (int64_t)2 * H * NL;
-        }
-        WETTS_TRY(launch_conv(fw.in_layers[i], p, s));
-        if (!gate) WETTS_TRY(k_gate(xin, B, H, Ty, acts, s));
-      }
-      const bool last = (i == NL - 1);
-      ConvParams p2 = conv_io(acts, H, Ty, rs, last ? H : 2 * H, B);
-      // residual / skip update in the conv's epilogue (rs never exists, one launch less per layer) where launches are
-      // the cost: the calls the small-launch conv kernel takes.  Big batches keep the specialised conv epilogue and
-      // the separate update -- the generic epilogue costs them 0.2 % of the headline step (profiles/r03_wn_fuse_ab.txt)
-      // ... and launches the LDS-DMA GEMM takes (gemm_pw.hip: h / skip rows come in through the accumulator init, so
-      // its epilogue stays a plain store; rows of the flow are 16-byte aligned here, see the top of this function)
-      const bool fuse_upd = m->wn_fuse == 2 ||
-                            (m->wn_fuse == 1 && ((int64_t)cdiv(last ? H : 2 * H, 64) * cdiv(Ty, 64) * B <= m->small_max_tiles ||
-                                                 (H % 32) == 0));
-      if (fuse_upd) {
-        p2.wn_h = h;
-        p2.wn_skip = skip;
-        p2.wn_mask = y_mask;
-        p2.wn_mask_stride = Ty;
-        p2.wn_H = H;
-        p2.wn_last = last ? 1 : 0;
-        p2.wn_first = i == 0 ? 1 : 0;
-      }
-      WETTS_TRY(launch_conv(fw.res_skip[i], p2, s));
-      if (!fuse_upd) WETTS_TRY(k_wn_update(rs, h, skip, y_mask, last ? 1 : 0, i == 0 ? 1 : 0, B, H, Ty, s));
-    }
+    WETTS_TRY(run_wn(m, fw.in_layers, fw.res_skip, wn16 ? &m->b_wn_in[f] : nullptr, wn16 ? &m->b_wn_rs[f] : nullptr,
+                     wn16, h, y_mask, use_g ? gl : nullptr, B, H, Ty, wsc, s));
     {
       ConvParams p = conv_io(skip, H, Ty, mm, I / 2, B);  // m = post(output*mask) * mask
       p.in_mask = y_mask;
@@ -1659,6 +1800,224 @@ int32_t wetts_flow_reverse(const wetts_model_t* m, const float* z_p_in, const fl
     cur = dst;
   }
   if (repad) WETTS_TRY(k_copy_rows(cur, Ty, Ty_in, z_out_user, Ty_in, Ty_in, (int64_t)B * I, s));
+  return WETTS_OK;
+}
+
+namespace wetts {
+static int32_t build_posterior(wetts_model* m, int spec, const float* blob_dev, int64_t numel, hipStream_t s) {
+  const wetts_config_t* c = &m->cfg;
+  const int H = c->hidden_channels, I = c->inter_channels;
+  build_posterior_layout(c, spec, m->post_layout);
+  WETTS_REQUIRE(numel == m->post_layout.total, "posterior blob has %lld floats, layout needs %lld", (long long)numel,
+                (long long)m->post_layout.total);
+  WETTS_HIP_CHECK(hipMalloc((void**)&m->post_blob, (size_t)numel * sizeof(float)));
+  WETTS_HIP_CHECK(hipMemcpyAsync(m->post_blob, blob_dev, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, s));
+  m->spec_channels = spec;
+  auto PT = [&](const std::string& name) -> const float* {
+    auto it = m->post_layout.index.find(name);
+    return it == m->post_layout.index.end() ? nullptr : m->post_blob + m->post_layout.specs[it->second].offset;
+  };
+  // pre: K = spec_channels (513: odd) -- the packing zero-fills the K tail of the last 16-channel chunk, and the conv
+  // kernels predicate the input channel, so the caller's spectrogram is read in place
+  WETTS_TRY(pack_conv_weight(PT("enc_q.pre.weight"), PT("enc_q.pre.bias"), H, spec, 1, 1, 0, 0, 0, s, &m->pe_pre));
+  m->pe_in.resize(kPostLayers);
+  m->pe_rs.resize(kPostLayers);
+  for (int i = 0; i < kPostLayers; ++i) {
+    // dilation_rate 1 (models.py:125-133): dilation 1, padding 2; rows interleaved for the gate epilogue like the flow's
+    WETTS_TRY(pack_conv_weight(PT(S("enc_q.enc.in_layers.%d.weight", i)), PT(S("enc_q.enc.in_layers.%d.bias", i)), 2 * H,
+                               H, kPostKernel, 1, (kPostKernel - 1) / 2, 0, 0, s, &m->pe_in[i], 0, m->wn_gate ? H : 0));
+    const int rs = (i < kPostLayers - 1) ? 2 * H : H;
+    WETTS_TRY(pack_conv_weight(PT(S("enc_q.enc.res_skip_layers.%d.weight", i)),
+                               PT(S("enc_q.enc.res_skip_layers.%d.bias", i)), rs, H, 1, 1, 0, 0, 0, s, &m->pe_rs[i]));
+  }
+  m->pe_cond_w = PT("enc_q.enc.cond_layer.weight");
+  m->pe_cond_b = PT("enc_q.enc.cond_layer.bias");
+  WETTS_TRY(pack_conv_weight(PT("enc_q.proj.weight"), PT("enc_q.proj.bias"), 2 * I, H, 1, 1, 0, 0, 0, s, &m->pe_proj));
+  // forward flow: x0 = x[:, :I/2] in natural order.  The pre_conv type's `pre` is packed that way already; every other
+  // type (plain, pre_conv2, the mono types' coupling layer) gets a second copy without the reversed input channels the
+  // reverse direction reads (build_model)
+  m->fwd_pre.resize(c->flow_n_flows);
+  if (c->transformer_flows != 1)
+    for (int f = 0; f < c->flow_n_flows; ++f) {
+      const std::string p = S("flow.flows.%d", flow_key_stride(c) * f);
+      WETTS_TRY(pack_conv_weight(m->T(p + ".pre.weight"), m->T(p + ".pre.bias"), H, I / 2, 1, 1, 0, 0, 0, s,
+                                 &m->fwd_pre[f]));
+    }
+  return WETTS_OK;
+}
+}  // namespace wetts
+
+int32_t wetts_load_posterior_encoder(wetts_model_t* m, int32_t spec_channels, const float* blob_dev, int64_t numel,
+                                     void* stream) {
+  WETTS_REQUIRE(m && blob_dev, "null argument");
+  WETTS_TRY(validate_posterior(&m->cfg, spec_channels));
+  hipStream_t s = (hipStream_t)stream;
+  // a reload replaces the previous copy; the caller has synchronised the streams that used it (set-up call)
+  free_posterior(m);
+  int32_t r = build_posterior(m, spec_channels, blob_dev, numel, s);
+  if (r == WETTS_OK) {
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      set_error("posterior weight packing failed: %s", hipGetErrorString(e));
+      r = WETTS_E_HIP;
+    }
+  }
+  if (r != WETTS_OK) {
+    free_posterior(m);
+    return r;
+  }
+  m->post_loaded = true;
+  return WETTS_OK;
+}
+
+int32_t wetts_posterior_encoder(const wetts_model_t* m, const float* y, const int64_t* y_lengths, const float* g,
+                                const float* eps, int32_t B, int32_t Ty_in, float* z, float* m_q, float* logs_q,
+                                float* y_mask, void* workspace, int64_t workspace_bytes, void* stream) {
+  WETTS_REQUIRE(m && y && y_lengths && eps && z && y_mask, "null argument");
+  WETTS_REQUIRE(m->post_loaded, "posterior encoder not loaded: call wetts_load_posterior_encoder first");
+  WETTS_REQUIRE(B >= 0 && Ty_in >= 0, "bad shape");
+  SmallConvScope small_scope(m->small_max_tiles);
+  if (B == 0 || Ty_in == 0) return WETTS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const wetts_config_t* c = &m->cfg;
+  const int H = c->hidden_channels, I = c->inter_channels, spec = m->spec_channels;
+  // rows of Ty = Ty_in rounded up to 4 frames, as in the flow (16-byte rows for the LDS-DMA GEMM and the k = 5
+  // staging); the extra frames have mask 0.  Only the pre conv reads the caller's [B, spec, Ty_in] rows.
+  const int Ty = (Ty_in + 3) & ~3;
+  Bump ws(workspace, workspace_bytes);
+  float* mask = ws.take<float>((int64_t)B * Ty);
+  float* h = ws.take<float>((int64_t)B * H * Ty);
+  WnScratch wsc{};
+  wsc.acts = ws.take<float>((int64_t)B * H * Ty);
+  wsc.skip = ws.take<float>((int64_t)B * H * Ty);
+  wsc.xin = ws.take<float>((int64_t)B * 2 * H * Ty);
+  wsc.rs = ws.take<float>((int64_t)B * 2 * H * Ty);
+  float* gl = ws.take<float>((int64_t)B * 2 * H * kPostLayers);
+  float* stats = ws.take<float>((int64_t)B * 2 * I * Ty);
+  if (!ws.ok) {
+    set_error("posterior_encoder: workspace too small");
+    return WETTS_E_WORKSPACE;
+  }
+  // x_mask = sequence_mask(y_lengths, Ty) (encoders.py:92-93)
+  WETTS_TRY(k_seq_mask(y_lengths, B, Ty_in, Ty, mask, y_mask, s));
+  {  // x = pre(y) * x_mask
+    ConvParams p = conv_io(y, spec, Ty, h, H, B);
+    p.x_bs = (int64_t)spec * Ty_in;
+    p.x_cs = Ty_in;
+    p.Tin = Ty_in;
+    p.out_mask = mask;
+    p.out_mask_stride = Ty;
+    WETTS_TRY(launch_conv(m->pe_pre, p, s));
+  }
+  // x = enc(x, x_mask, g)  (WN, 16 layers, k = 5, f32)
+  const bool use_g = g && m->pe_cond_w;
+  if (use_g) WETTS_TRY(k_cond_linear(g, m->pe_cond_w, m->pe_cond_b, B, 2 * H * kPostLayers, c->gin_channels, gl, s));
+  WETTS_TRY(run_wn(m, m->pe_in, m->pe_rs, nullptr, nullptr, 0, h, mask, use_g ? gl : nullptr, B, H, Ty, wsc, s));
+  {  // stats = proj(output * x_mask) * x_mask
+    ConvParams p = conv_io(wsc.skip, H, Ty, stats, 2 * I, B);
+    p.in_mask = mask;
+    p.in_mask_stride = Ty;
+    p.out_mask = mask;
+    p.out_mask_stride = Ty;
+    WETTS_TRY(launch_conv(m->pe_proj, p, s));
+  }
+  // m, logs = split(stats);  z = (m + eps * exp(logs)) * x_mask  (one element-wise pass, into the caller's rows)
+  return k_posterior_sample(stats, eps, mask, B, I, Ty_in, Ty, z, m_q, logs_q, s);
+}
+
+int32_t wetts_flow_forward(const wetts_model_t* m, const float* z_in, const float* y_mask_in, const float* g, int32_t B,
+                           int32_t Ty_in, float* z_p_user, void* workspace, int64_t workspace_bytes, void* stream) {
+  WETTS_REQUIRE(m && z_in && y_mask_in && z_p_user, "null argument");
+  WETTS_REQUIRE(m->post_loaded, "flow_forward: call wetts_load_posterior_encoder first (it packs the forward weights)");
+  SmallConvScope small_scope(m->small_max_tiles);
+  if (B == 0 || Ty_in == 0) return WETTS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const wetts_config_t* c = &m->cfg;
+  const int H = c->hidden_channels, I = c->inter_channels, NL = c->flow_wn_layers, Hh = I / 2;
+  const int tf = c->transformer_flows;
+  Bump ws(workspace, workspace_bytes);
+  const int Ty = (Ty_in + 3) & ~3;  // rows of 4 frames, as in wetts_flow_reverse
+  const bool repad = Ty != Ty_in;
+  FlowScratch fs;
+  if (!take_flow_scratch(m, B, Ty, repad, ws, fs)) {
+    set_error("flow_forward: workspace too small");
+    return WETTS_E_WORKSPACE;
+  }
+  const int wn16 = m->flow_precision;
+  if (wn16) WETTS_TRY(pack_flow_bf16(m, s));
+  const float* y_mask = y_mask_in;
+  const float* cur = z_in;
+  if (repad) {
+    WETTS_TRY(k_copy_rows(z_in, Ty_in, Ty_in, fs.zp_pad, Ty, Ty, (int64_t)B * I, s));
+    WETTS_TRY(k_copy_rows(y_mask_in, Ty_in, Ty_in, fs.mask_pad, Ty, Ty, B, s));
+    cur = fs.zp_pad;
+    y_mask = fs.mask_pad;
+  }
+  // the next ping-pong buffer; the last write of the pass goes straight to the caller's tensor when rows are unpadded
+  auto next = [&](bool final_write) { return (final_write && !repad) ? z_p_user : (cur == fs.xa ? fs.xb : fs.xa); };
+  const bool use_g = has_g(c) && g;
+  for (int f = 0; f < c->flow_n_flows; ++f) {  // module order: [layer, Flip] (+ Mono for the mono_layer_* types)
+    const FlowW& fw = m->flows[f];
+    const bool last = f == c->flow_n_flows - 1;
+    // coupling layer on x0 = x[:, :I/2] (natural order)
+    if (tf == 1) {
+      // pre_conv (flows.py:145-150): x0_ = pre_transformer(x0 * mask, mask) + x0;  h = pre(x0_) * mask
+      WETTS_TRY(k_mono_split(cur, y_mask, B, I, Ty, 1.f, fs.tx0, fs.txm, s));  // x0, x0 * mask
+      WETTS_TRY(run_enc_layers(fw.pre_tr, fs.txm, y_mask, B, Hh, Hh, 2, -1, Ty, fs.tq, fs.tk, fs.tv, fs.tatt, fs.ty,
+                               fs.thid, fs.tsc, fs.txb, s));
+      WETTS_TRY(k_add(fs.txm, fs.tx0, (int64_t)B * Hh * Ty, fs.txm, s));
+      ConvParams p = conv_io(fs.txm, Hh, Ty, fs.h, H, B);
+      p.out_mask = y_mask;
+      p.out_mask_stride = Ty;
+      WETTS_TRY(launch_conv(fw.pre, p, s));
+    } else {
+      ConvParams p = conv_io(cur, Hh, Ty, fs.h, H, B);  // h = pre(x0) * mask, the natural-order copy
+      p.x_bs = (int64_t)I * Ty;
+      p.out_mask = y_mask;
+      p.out_mask_stride = Ty;
+      WETTS_TRY(launch_conv(m->fwd_pre[f], p, s));
+      if (tf == 2) {
+        // pre_conv2 (flows.py:64-67): h = h + pre_transformer(h * mask, mask)
+        WETTS_HIP_CHECK(hipMemcpyAsync(fs.txm, fs.h, (size_t)B * H * Ty * sizeof(float), hipMemcpyDeviceToDevice, s));
+        WETTS_TRY(run_enc_layers(fw.pre_tr, fs.txm, y_mask, B, H, H, 2, 4, Ty, fs.tq, fs.tk, fs.tv, fs.tatt, fs.ty,
+                                 fs.thid, fs.tsc, fs.txb, s));
+        WETTS_TRY(k_add(fs.h, fs.txm, (int64_t)B * H * Ty, fs.h, s));
+      }
+    }
+    if (use_g) WETTS_TRY(k_cond_linear(g, fw.cond_w, fw.cond_b, B, 2 * H * NL, c->gin_channels, fs.gl, s));
+    WETTS_TRY(run_wn(m, fw.in_layers, fw.res_skip, wn16 ? &m->b_wn_in[f] : nullptr, wn16 ? &m->b_wn_rs[f] : nullptr,
+                     wn16, fs.h, y_mask, use_g ? fs.gl : nullptr, B, H, Ty, fs.wn, s));
+    {
+      ConvParams p = conv_io(fs.wn.skip, H, Ty, fs.mm, Hh, B);  // m = post(output * mask) * mask
+      p.in_mask = y_mask;
+      p.in_mask_stride = Ty;
+      p.out_mask = y_mask;
+      p.out_mask_stride = Ty;
+      WETTS_TRY(launch_conv(fw.post, p, s));
+    }
+    // x1 = m + x1 * mask, then Flip
+    float* dst = next(last && !mono_flows(c));
+    WETTS_TRY(k_coupling_fwd_flip(cur, fs.mm, y_mask, B, I, Ty, dst, s));
+    cur = dst;
+    if (mono_flows(c)) {
+      // MonoTransformerFlowLayer.forward (flows.py:275-286, 312-318) on x0 = x[:, :I/2]:
+      //   inter (3): m = post(pre_transformer(x0 * mask, mask) + x0) * mask;  out = [x0, m + x1 * mask]
+      //   post  (4): m = post(pre_transformer(x0, mask)) * mask (the Encoder masks its input itself);
+      //              out = x + [x0, m + x1 * mask]
+      WETTS_TRY(k_mono_split(cur, y_mask, B, I, Ty, 1.f, fs.tx0, fs.txm, s));
+      WETTS_TRY(run_enc_layers(fw.mono_tr, fs.txm, y_mask, B, Hh, Hh, 2, -1, Ty, fs.tq, fs.tk, fs.tv, fs.tatt, fs.ty,
+                               fs.thid, fs.tsc, fs.txb, s));
+      if (tf == 3) WETTS_TRY(k_add(fs.txm, fs.tx0, (int64_t)B * Hh * Ty, fs.txm, s));
+      ConvParams p = conv_io(fs.txm, Hh, Ty, fs.mm, Hh, B);
+      p.out_mask = y_mask;
+      p.out_mask_stride = Ty;
+      WETTS_TRY(launch_conv(fw.mono_post, p, s));
+      dst = next(last);
+      WETTS_TRY(k_mono_coupling_fwd(cur, fs.mm, y_mask, B, I, Ty, tf == 4 ? 1 : 0, dst, s));
+      cur = dst;
+    }
+  }
+  if (repad) WETTS_TRY(k_copy_rows(cur, Ty, Ty_in, z_p_user, Ty_in, Ty_in, (int64_t)B * I, s));
   return WETTS_OK;
 }
 

@@ -3,9 +3,9 @@
 C ABI in include/wetts_hip.h.  PyTorch is used for device memory, streams and nothing else:
 there is no eager / CPU fallback anywhere in this module.
 
-Same constructor arguments, same `infer` / `infer_encoder` / `export_*` signatures and return
-tuples as the reference; training-only members (`forward`, `voice_conversion`, `enc_q`) are out of
-scope and raise.
+Same constructor arguments, same `infer` / `infer_encoder` / `export_*` / `voice_conversion` signatures and
+return tuples as the reference; training (`forward`) is out of scope and raises.  The posterior
+encoder (`enc_q`) is loaded when the checkpoint carries it and runs only inside `voice_conversion`.
 
 Extra, optional keyword arguments (not in the reference): `eps_w` / `eps_z` inject the two
 standard-normal draws the reference makes with torch.randn (duration_predictors.py:257,
@@ -87,6 +87,8 @@ class SynthesizerTrn:
             self.hop_length = int(self.cfg.istft_hop_length)
         self.device = torch.device("cpu")
         self._blob = None      # CPU float32 blob (weights live here until .to(device))
+        self._post_blob = None  # CPU float32 blob of enc_q.* (voice conversion), when the checkpoint carries it
+        self._post_on_device = False  # uploaded by the first voice_conversion() call (wetts_load_posterior_encoder)
         self._handle = None    # wetts_model_t*
         self._ws = _Workspace()
         self._ws_dec = _Workspace()  # the decoder's own scratch in overlap mode (see set_overlap)
@@ -212,8 +214,13 @@ class SynthesizerTrn:
         return checkpoint.blob_layout(self.cfg)
 
     def load_state_dict(self, state_dict, strict=True):
-        """Accepts the reference's `G_*.pth["model"]` dict (weight-norm pairs folded here)."""
+        """Accepts the reference's `G_*.pth["model"]` dict (weight-norm pairs folded here).  The posterior encoder's
+        `enc_q.*` tensors are kept (as a host blob, uploaded by the first voice_conversion() call) when the dict carries
+        all of them; a dict without them loads as before and voice_conversion() then raises."""
         self._blob = checkpoint.pack_blob(self.cfg, state_dict, strict=strict)
+        self._post_blob = None
+        if checkpoint.has_posterior(self.cfg, self.spec_channels, state_dict):
+            self._post_blob = checkpoint.pack_posterior_blob(self.cfg, self.spec_channels, state_dict)
         self._destroy()
         if self.device.type == "cuda":
             self._create()
@@ -243,6 +250,10 @@ class SynthesizerTrn:
             fwd, inv = _onnx_stft_bases(int(self.cfg.istft_n_fft), int(self.cfg.istft_hop_length))
             sd["dec.stft.forward_basis"] = fwd.to(blob.device)
             sd["dec.stft.inverse_basis"] = inv.to(blob.device)
+        if self._post_blob is not None:  # enc_q.* (folded), only when the loaded checkpoint carried them
+            pb = self._post_blob.to(blob.device)
+            for name, off, numel, shape in checkpoint.posterior_layout(self.cfg, self.spec_channels):
+                sd[name] = pb[off:off + numel].view(shape)
         return sd
 
     def load_blob(self, blob):
@@ -284,6 +295,7 @@ class SynthesizerTrn:
         if self._handle is not None:
             _lib.load().wetts_destroy(self._handle)
             self._handle = None
+        self._post_on_device = False
 
     def __del__(self):
         try:
@@ -315,8 +327,87 @@ class SynthesizerTrn:
         # net_g.export_forward` (export_onnx.py:82,94,127) and then call the module
         return self.forward(*a, **k)
 
-    def voice_conversion(self, *a, **k):
-        raise NotImplementedError("voice_conversion needs the posterior encoder (out of scope)")
+    # ---- voice conversion (models.py:369-376) ------------------------------------------------------
+    def _require_posterior(self):
+        """The posterior encoder on the device: uploaded on first use, so a model used only for infer() holds no copy."""
+        lib = self._require()
+        if self._post_blob is None:
+            raise _lib.WettsError("voice_conversion needs the posterior encoder, but the loaded checkpoint has no "
+                                  "enc_q.* tensors")
+        if not self._post_on_device:
+            with torch.cuda.device(self.device):
+                dev = self._post_blob.to(self.device)
+                _lib.check(lib.wetts_load_posterior_encoder(self._handle, int(self.spec_channels), _lib.ptr(dev),
+                                                            dev.numel(), _lib.current_stream_ptr()),
+                           "load_posterior_encoder")
+            self._post_on_device = True
+        return lib
+
+    def _flow_pass(self, z, y_mask, g, reverse, ws, nws):
+        """flow(z, y_mask, g, reverse) on [B, inter, Ty] / [B, Ty] device tensors -> a new tensor."""
+        lib = _lib.load()
+        B, _, Ty = z.shape
+        out = torch.empty_like(z)
+        fn = lib.wetts_flow_reverse if reverse else lib.wetts_flow_forward
+        _lib.check(fn(self._handle, _lib.ptr(z), _lib.ptr(y_mask), _lib.ptr(g), B, Ty, _lib.ptr(out), _lib.ptr(ws), nws,
+                      _lib.current_stream_ptr()), "flow_reverse" if reverse else "flow_forward")
+        return out
+
+    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, eps_q=None):
+        """models.py:369-376: the utterance in linear spectrogram `y` [B, spec_channels, Ty] (the reference's
+        `spectrogram_torch(audio, filter_length, sampling_rate, hop_length, win_length)`), spoken by `sid_src`, in the
+        voice of `sid_tgt`.  Returns (o_hat [B,1,Ty*hop], y_mask [B,1,Ty], (z, z_p, z_hat) [B,inter,Ty]).
+
+        Stages: emb_g -> posterior encoder (g_src) -> flow (g_src) -> flow^-1 (g_tgt) -> dec(z_hat * y_mask, g_tgt),
+        all on the caller's stream.  `eps_q` (optional, not in the reference) injects the torch.randn_like draw of the
+        posterior sample (encoders.py:98); without it the draw comes from the library's Philox kernel on the device
+        generator's stream, so torch.manual_seed makes a call reproducible as it does for infer().  Speaker ids outside
+        the table raise IndexError after the call's one host read-back of the status word."""
+        if self.n_speakers <= 0:  # the reference has no emb_g then (models.py:159-160)
+            raise AttributeError("'SynthesizerTrn' object has no attribute 'emb_g'")
+        lib = self._require_posterior()
+        y = self._f32(y)
+        if y.dim() != 3 or y.shape[1] != self.spec_channels:
+            raise ValueError(f"y must be [B, {self.spec_channels}, Ty], got {tuple(y.shape)}")
+        B, _, Ty = y.shape
+        I = self.inter_channels
+        y_lengths = self._ids(y_lengths)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if eps_q is None:
+            eps_q = self._randn(B, I, Ty)
+        else:
+            eps_q = self._f32(eps_q)
+            if tuple(eps_q.shape) != (B, I, Ty):
+                raise ValueError(f"eps_q must be [{B},{I},{Ty}], got {tuple(eps_q.shape)}")
+        # the decoder's own workspace in overlap mode (the encoder side stream may still be using self._ws)
+        nws = max(int(lib.wetts_posterior_workspace_bytes(self._handle, B, Ty)),
+                  int(lib.wetts_workspace_bytes(self._handle, B, 0, Ty)))
+        ws = (self._ws_dec if self.overlap else self._ws).get(nws, self.device)
+        s = _lib.current_stream_ptr()
+        status = torch.empty(1, dtype=torch.int64, device=self.device)
+        _lib.check(lib.wetts_set_status_word(self._handle, _lib.ptr(status), s), "set_status_word")
+        try:
+            sids = torch.stack([self._ids(sid_src).reshape(B), self._ids(sid_tgt).reshape(B)])
+            g = torch.empty(2, B, self.gin_channels, **f32)
+            _lib.check(lib.wetts_speaker_embedding(self._handle, _lib.ptr(sids), 2 * B, _lib.ptr(g), s),
+                       "speaker_embedding")
+        finally:
+            lib.wetts_set_status_word(self._handle, None, s)
+        g_src, g_tgt = g[0], g[1]
+        z, m_q, logs_q = (torch.empty(B, I, Ty, **f32) for _ in range(3))
+        y_mask = torch.empty(B, Ty, **f32)
+        _lib.check(lib.wetts_posterior_encoder(self._handle, _lib.ptr(y), _lib.ptr(y_lengths), _lib.ptr(g_src),
+                                               _lib.ptr(eps_q), B, Ty, _lib.ptr(z), _lib.ptr(m_q), _lib.ptr(logs_q),
+                                               _lib.ptr(y_mask), _lib.ptr(ws), nws, s), "posterior_encoder")
+        z_p = self._flow_pass(z, y_mask, g_src, False, ws, nws)
+        z_hat = self._flow_pass(z_p, y_mask, g_tgt, True, ws, nws)
+        o_hat = self._decode(z_hat, g_tgt, y_mask, Ty)
+        self.last_status = int(status.cpu().item()) & 0xFFFFFFFF  # the call's one host sync
+        if self.last_status & _lib.STATUS_SPEAKER_ID_RANGE:
+            raise IndexError("index out of range in self (sid outside emb_g, models.py:370-371)")
+        self._last_vc = dict(z=z, m_q=m_q, logs_q=logs_q, z_p=z_p, z_hat=z_hat, y_mask=y_mask, g_src=g_src,
+                             g_tgt=g_tgt)
+        return o_hat, y_mask.unsqueeze(1), (z, z_p, z_hat)
 
     # ---- stages ----------------------------------------------------------------------------------
     def _ids(self, t):

@@ -101,6 +101,44 @@ def make_state_dict(cfg, seed=0):
     return sd
 
 
+_POSTERIOR_WN = re.compile(r"^enc_q\.enc\.(in_layers\.\d+|res_skip_layers\.\d+|cond_layer)\.weight$")
+
+
+def make_posterior_state_dict(cfg, spec_channels, seed=0):
+    """Reference-keyed `enc_q.*` tensors (PosteriorEncoder, encoders.py:60-99) for `cfg`, deterministic in `seed`, from
+    a generator of their own (make_state_dict's stream, and so every stored blob checksum, is untouched).  The WN layers
+    carry weight-norm pairs like a reference checkpoint (modules.py:35,49,58).  The pre conv is scaled for linear
+    spectrogram input (magnitudes of up to a few hundred for a loud harmonic at n_fft 1024) and the projection for
+    log-scales of a few tenths, so the posterior sample is O(1)."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    for name, _, _, shape in checkpoint.posterior_layout(cfg, spec_channels):
+        w = torch.randn(*shape, generator=g, dtype=torch.float32)
+        if name.endswith(".bias"):
+            sd[name] = 0.05 * w
+            continue
+        if name == "enc_q.pre.weight":
+            w = w * (0.05 / math.sqrt(shape[1]))
+        elif name == "enc_q.proj.weight":
+            w = w * (0.3 / math.sqrt(shape[1]))
+        elif name.endswith("cond_layer.weight"):
+            w = w * (0.3 / math.sqrt(shape[1]))
+        elif ".res_skip_layers." in name:
+            w = w * (0.5 / math.sqrt(shape[1]))
+        else:
+            w = w * (1.0 / math.sqrt(shape[1] * shape[2]))
+        if _POSTERIOR_WN.match(name):
+            dims = tuple(range(1, w.dim()))
+            norm = torch.linalg.vector_norm(w, ord=2, dim=dims, keepdim=True)
+            gain = norm * (1.0 + 0.05 * torch.randn(shape[0], *([1] * (w.dim() - 1)), generator=g))
+            base = name[:-len("weight")]
+            sd[base + "weight_g"] = gain
+            sd[base + "weight_v"] = w
+        else:
+            sd[name] = w
+    return sd
+
+
 def blob_checksum(blob):
     """Order-sensitive fingerprint of a float32 blob (guards golden fixtures against RNG drift)."""
     b = blob.detach().to(torch.float64)
