@@ -1,16 +1,21 @@
 """ORACLE -- TEST INFRASTRUCTURE ONLY.  Never imported by the product path (wetts_amd/).
 
-A CPU float32 restatement of the reference's SynthesizerTrn.infer() hot path (wenet-e2e/wetts,
-wetts/vits/model/models.py:228-280) as plain functions over a dict of *folded* weights
-(name -> tensor, weight-norm already collapsed).  Because the kernels under test are floating
-point, the restatement is written with torch CPU tensor ops (the task's "torch fp32 reference for
-a floating-point kernel"), but it is a restatement, not the reference's nn.Modules: the
-relative-position attention is the direct banded form, generate_path is an index search, Flip is
-index arithmetic, and ConvTranspose1d is not special-cased anywhere else.
+A CPU restatement of the reference's SynthesizerTrn.infer() hot path (wenet-e2e/wetts,
+wetts/vits/model/models.py:228-280) and of its voice_conversion() (models.py:369-376: the posterior
+encoder, the forward flow, flow^-1 and the decoder) as plain functions over a dict of *folded*
+weights (name -> tensor, weight-norm already collapsed).  Because the kernels under test are
+floating point, the restatement is written with torch CPU tensor ops (the task's "torch fp32
+reference for a floating-point kernel"), but it is a restatement, not the reference's nn.Modules:
+the relative-position attention is the direct banded form, generate_path is an index search, Flip
+is index arithmetic, and ConvTranspose1d is not special-cased anywhere else.  The functions follow
+the dtype of their inputs: float64 weights and inputs give a float64 result (the 16-bit numerics
+specs, the uint8 graph and the Philox draw are the exceptions; they fix their own types).
 
 Pinning: tests/test_oracle_golden.py checks every function here against golden vectors produced
 by the *real* reference run in the build container (tests/golden/make_golden.py, fixtures under
-tests/golden/*.npz) and, when /root/reference is present, against the live reference.
+tests/golden/*.npz) and, when /root/reference is present, against the live reference;
+tests/test_cpu_voice_conversion.py holds the voice-conversion functions to tests/golden/vc_*.npz
+(tests/golden/make_golden_vc.py).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 Each function cites the reference file:line it follows (paths relative to wetts/vits/).
@@ -342,12 +347,37 @@ def mono_flow_reverse(W, pre, x, y_mask, residual_connection):
     return torch.cat([x0, x1], 1)
 
 
+def _coupling_mean(W, cfg, pre, x0, y_mask, g, wn_dtype):
+    """The mean m = post(enc(pre(x0))) * mask of one mean_only coupling layer -- the part both directions share
+    (RCL flows.py:494-504; pre_conv :147-164; pre_conv2 :63-74).  wn_dtype: the 16-bit WaveNet numerics spec."""
+    H = cfg["hidden_channels"]
+    tf = cfg.get("transformer_flows", 0)
+    if tf == 1:
+        # "pre_conv" = ResidualCouplingTransformersLayer (flows.py:95-177): a 2-layer,
+        # 2-head, window-less Encoder on x0 with a residual, ahead of `pre`
+        x0_ = encoder_stack(W, pre + ".pre_transformer", x0 * y_mask, y_mask, 2, 2, None, 3)
+        h = conv1d(W, pre + ".pre", x0_ + x0) * y_mask
+    elif tf == 2:
+        # "pre_conv2" = ResidualCouplingTransformersLayer2 (flows.py:16-92): one Encoder layer
+        # (2 heads, relative window 4, FFN kernel = the flow's kernel size) on pre(x0)
+        h = conv1d(W, pre + ".pre", x0) * y_mask
+        h = h + encoder_stack(W, pre + ".pre_transformer", h * y_mask, y_mask, 1, 2, 4,
+                              cfg["flow_kernel_size"])
+    else:
+        h = conv1d(W, pre + ".pre", x0) * y_mask
+    if wn_dtype is None:
+        h = wn(W, pre + ".enc", h, y_mask, g, H, cfg["flow_wn_layers"], cfg["flow_kernel_size"])
+    else:
+        h = wn_16bit_sim(W, pre + ".enc", h, y_mask, g, H, cfg["flow_wn_layers"],
+                         cfg["flow_kernel_size"], wn_dtype)
+    return conv1d(W, pre + ".post", h) * y_mask
+
+
 def flow_reverse(W, cfg, z_p, y_mask, g, wn_dtype=None):
     """ResidualCouplingTransformersBlock.forward(reverse=True): reversed [(RCL, Flip) x n], or
     [(RCL, Flip, Mono) x n] for the mono_layer types (flows.py:442-449); RCL reverse with mean_only (flows.py:494-513).  wn_dtype (torch.bfloat16 /
     torch.float16): the 16-bit WaveNet numerics spec instead of the f32 graph."""
-    H, I = cfg["hidden_channels"], cfg["inter_channels"]
-    half = I // 2
+    half = cfg["inter_channels"] // 2
     x = z_p
     tf = cfg.get("transformer_flows", 0)
     for f in range(cfg["flow_n_flows"] - 1, -1, -1):
@@ -358,28 +388,62 @@ def flow_reverse(W, cfg, z_p, y_mask, g, wn_dtype=None):
         x = torch.flip(x, [1])
         pre = f"flow.flows.{(3 if tf >= 3 else 2) * f}"
         x0, x1 = x[:, :half], x[:, half:]
-        if cfg.get("transformer_flows", 0) == 1:
-            # "pre_conv" = ResidualCouplingTransformersLayer (flows.py:95-177): a 2-layer,
-            # 2-head, window-less Encoder on x0 with a residual, ahead of `pre`
-            x0_ = encoder_stack(W, pre + ".pre_transformer", x0 * y_mask, y_mask, 2, 2, None, 3)
-            h = conv1d(W, pre + ".pre", x0_ + x0) * y_mask
-        elif cfg.get("transformer_flows", 0) == 2:
-            # "pre_conv2" = ResidualCouplingTransformersLayer2 (flows.py:16-92): one Encoder layer
-            # (2 heads, relative window 4, FFN kernel = the flow's kernel size) on pre(x0)
-            h = conv1d(W, pre + ".pre", x0) * y_mask
-            h = h + encoder_stack(W, pre + ".pre_transformer", h * y_mask, y_mask, 1, 2, 4,
-                                  cfg["flow_kernel_size"])
-        else:
-            h = conv1d(W, pre + ".pre", x0) * y_mask
-        if wn_dtype is None:
-            h = wn(W, pre + ".enc", h, y_mask, g, H, cfg["flow_wn_layers"], cfg["flow_kernel_size"])
-        else:
-            h = wn_16bit_sim(W, pre + ".enc", h, y_mask, g, H, cfg["flow_wn_layers"],
-                             cfg["flow_kernel_size"], wn_dtype)
-        m = conv1d(W, pre + ".post", h) * y_mask
+        m = _coupling_mean(W, cfg, pre, x0, y_mask, g, wn_dtype)
         x1 = (x1 - m) * y_mask
         x = torch.cat([x0, x1], 1)
     return x
+
+
+def mono_flow_forward(W, pre, x, y_mask, residual_connection):
+    """MonoTransformerFlowLayer.forward(reverse=False) with mean_only=True (logs = 0).
+    residual_connection=True ("mono_layer_post_residual", flows.py:274-290): m = post(pre_transformer(x0)) * mask (the
+    Encoder masks its input itself, attentions.py:70-72), then x + cat(x0, m + x1 * mask).  False (:305-320): the Encoder
+    output gets the x0 residual and x1 <- m + x1 * mask."""
+    half = x.shape[1] // 2
+    x0, x1 = x[:, :half], x[:, half:]
+    if residual_connection:
+        h = encoder_stack(W, pre + ".pre_transformer", x0, y_mask, 2, 2, None, 3)
+        m = conv1d(W, pre + ".post", h) * y_mask
+        return x + torch.cat([x0, m + x1 * y_mask], 1)
+    h = encoder_stack(W, pre + ".pre_transformer", x0 * y_mask, y_mask, 2, 2, None, 3) + x0
+    m = conv1d(W, pre + ".post", h) * y_mask
+    return torch.cat([x0, m + x1 * y_mask], 1)
+
+
+def flow_forward(W, cfg, z, y_mask, g, wn_dtype=None):
+    """ResidualCouplingTransformersBlock.forward(reverse=False) (flows.py:442-445): the modules in build order,
+    [(coupling, Flip) x n] or [(RCL, Flip, Mono) x n] for the mono_layer types (:391-425).  Coupling forward with
+    mean_only (logs = 0): x1 <- m + x1 * mask (RCL flows.py:494-509; pre_conv :147-169; pre_conv2 :63-79).
+    wn_dtype: the 16-bit WaveNet numerics spec, as in flow_reverse."""
+    half = cfg["inter_channels"] // 2
+    tf = cfg.get("transformer_flows", 0)
+    x = z
+    for f in range(cfg["flow_n_flows"]):
+        pre = f"flow.flows.{(3 if tf >= 3 else 2) * f}"
+        x0, x1 = x[:, :half], x[:, half:]
+        m = _coupling_mean(W, cfg, pre, x0, y_mask, g, wn_dtype)
+        x = torch.flip(torch.cat([x0, m + x1 * y_mask], 1), [1])  # Flip (modules.py:100-104)
+        if tf >= 3:
+            x = mono_flow_forward(W, f"flow.flows.{3 * f + 2}", x, y_mask, residual_connection=(tf == 4))
+    return x
+
+
+# ------------------------------------------------------------------------------------------------
+# posterior encoder  (model/encoders.py:60-99)
+# ------------------------------------------------------------------------------------------------
+POSTERIOR_WN_LAYERS, POSTERIOR_KERNEL = 16, 5  # PosteriorEncoder(spec, inter, hidden, 5, 1, 16, gin), models.py:124-132
+
+
+def posterior_encoder(W, cfg, y, y_lengths, g, eps):
+    """PosteriorEncoder.forward (encoders.py:91-99); eps [B,inter,Ty] replaces the torch.randn_like draw at :98.
+    Returns (z, m, logs, y_mask [B,1,Ty])."""
+    y_mask = sequence_mask(y_lengths, y.shape[2]).unsqueeze(1).to(y.dtype)
+    x = conv1d(W, "enc_q.pre", y) * y_mask
+    x = wn(W, "enc_q.enc", x, y_mask, g, cfg["hidden_channels"], POSTERIOR_WN_LAYERS, POSTERIOR_KERNEL)
+    stats = conv1d(W, "enc_q.proj", x) * y_mask
+    m, logs = torch.split(stats, cfg["inter_channels"], dim=1)
+    z = (m + eps * torch.exp(logs)) * y_mask
+    return z, m, logs, y_mask
 
 
 # ------------------------------------------------------------------------------------------------
@@ -689,6 +753,25 @@ def infer(W, cfg, x_ids, x_lengths, sid=None, noise_scale=1.0, length_scale=1.0,
                     y_lengths=y_lengths, y_mask=y_mask, attn=attn, f2p=f2p, m_p_exp=m_e,
                     logs_p_exp=logs_e, z_p=z_p, z=z, o=o, g=g)
     return o, attn, y_mask, (z, z_p, m_e, logs_e)
+
+
+# ------------------------------------------------------------------------------------------------
+# voice conversion  (model/models.py:369-376)
+# ------------------------------------------------------------------------------------------------
+def voice_conversion(W, cfg, y, y_lengths, sid_src, sid_tgt, eps, return_stages=False):
+    """SynthesizerTrn.voice_conversion: posterior encoder (g_src) -> flow (g_src) -> flow^-1 (g_tgt) ->
+    dec(z_hat * y_mask, g_tgt).  eps replaces the posterior's randn_like draw.  Returns (o_hat, y_mask, (z, z_p, z_hat)),
+    or with return_stages a dict that also holds m_q and logs_q."""
+    with torch.no_grad():
+        g_src = F.embedding(sid_src, W["emb_g.weight"]).unsqueeze(-1)
+        g_tgt = F.embedding(sid_tgt, W["emb_g.weight"]).unsqueeze(-1)
+        z, m_q, logs_q, y_mask = posterior_encoder(W, cfg, y, y_lengths, g_src, eps)
+        z_p = flow_forward(W, cfg, z, y_mask, g_src)
+        z_hat = flow_reverse(W, cfg, z_p, y_mask, g_tgt)
+        o_hat = decoder(W, cfg, z_hat * y_mask, g_tgt)
+    if return_stages:
+        return dict(z=z, m_q=m_q, logs_q=logs_q, y_mask=y_mask, z_p=z_p, z_hat=z_hat, o_hat=o_hat)
+    return o_hat, y_mask, (z, z_p, z_hat)
 
 
 def audio_to_int16(audio):

@@ -119,3 +119,67 @@ def test_new_kernels_have_no_scratch_and_full_occupancy():
         assert k in table, k
         # element-wise kernels: no spills, and few enough registers for eight waves per SIMD
         assert table[k]["ScratchSize"] == 0 and table[k]["VGPRs"] <= 64, (k, table[k])
+
+
+# ---- the oracle's voice conversion (oracle/vits_oracle.py) pinned to the reference's goldens --------------------------
+VC_CASES = ["vc_tiny_b3", "vc_vits2_v1_b2", "vc_tiny_preconv2_spk_b3", "vc_tiny_mono_post_b2", "vc_tiny_mono_inter_b3",
+            "vc_tiny_vocos_b2", "vc_aishell3_b4x600"]
+# one fixture per flow type: plain, pre_conv, pre_conv2, mono_layer_post_residual, mono_layer_inter_residual
+FLOW_TYPE_CASES = VC_CASES[:5]
+
+
+@pytest.mark.parametrize("name", VC_CASES)
+def test_oracle_voice_conversion_matches_reference_golden(name):
+    """oracle.voice_conversion at f32 on the fixture's input and injected draw against the live reference's outputs:
+    y_mask equal, every stage within 1e-5 rel RMS, audio within 1e-5 abs RMS (the full-size fixture: its stored
+    strided sub-samples)."""
+    from oracle import vits_oracle as vo
+    case = util.load_vc_case(name)
+    cfg, sd, psd = util.vc_case_model(case, SPEC)
+    W = util.vc_weights(cfg, sd, psd)
+    st = vo.voice_conversion(W, util.cfg_dict(cfg), torch.from_numpy(case["y"]), torch.from_numpy(case["y_lengths"]),
+                             torch.from_numpy(case["sid_src"]), torch.from_numpy(case["sid_tgt"]),
+                             torch.from_numpy(case["eps"]), return_stages=True)
+    assert np.array_equal(st["y_mask"].numpy(), case["y_mask"])
+    rows = {}
+    if "sub_strides" in case:
+        sa, sz = (int(v) for v in case["sub_strides"])
+        assert tuple(st["o_hat"].shape) == tuple(int(v) for v in case["audio_shape"])
+        for k in ("z", "m_q", "logs_q", "z_p", "z_hat"):
+            rows[k] = util.rel_rms(st[k].numpy()[..., ::sz], case[k + "_sub"])
+        rows["audio_abs_rms"] = util.rms(st["o_hat"].numpy()[..., ::sa] - case["audio_sub"])
+    else:
+        for k in ("z", "m_q", "logs_q", "z_p", "z_hat"):
+            rows[k] = util.rel_rms(st[k].numpy(), case[k])
+        assert st["o_hat"].shape == case["audio"].shape
+        rows["audio_abs_rms"] = util.rms(st["o_hat"].numpy() - case["audio"])
+    print(name, "oracle vs reference", rows)
+    for k, v in rows.items():
+        assert v < 1e-5, (k, rows)
+
+
+@pytest.mark.parametrize("name", FLOW_TYPE_CASES)
+def test_oracle_flow_round_trip_float64(name):
+    """flow_reverse(flow_forward(z)) == z on valid frames to 1e-12 in float64, for every flow type (mean-only couplings
+    are exact inverses on mask-1 frames), and the forward flow is not the identity."""
+    from oracle import vits_oracle as vo
+    case = util.load_vc_case(name)
+    cfg, sd, psd = util.vc_case_model(case, SPEC)
+    W = util.vc_weights(cfg, sd, psd, torch.float64)
+    cd = util.cfg_dict(cfg)
+    yl = torch.from_numpy(case["y_lengths"])
+    B, Ty = len(yl), int(case["y"].shape[2])
+    y_mask = (torch.arange(Ty)[None, :] < yl[:, None]).to(torch.float64).unsqueeze(1)
+    z = torch.randn(B, cd["inter_channels"], Ty, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+    z = z * y_mask
+    g = torch.nn.functional.embedding(torch.from_numpy(case["sid_src"]), W["emb_g.weight"]).unsqueeze(-1)
+    with torch.no_grad():
+        z_p = vo.flow_forward(W, cd, z, y_mask, g)
+        back = vo.flow_reverse(W, cd, z_p, y_mask, g)
+    assert z_p.dtype == back.dtype == torch.float64
+    valid = y_mask.bool().expand_as(z)
+    err = float((back - z)[valid].abs().max())
+    moved = util.rel_rms(z_p[valid].numpy(), z[valid].numpy())
+    print(name, "float64 round trip max |error|", err, "forward flow moves z by", moved)
+    assert moved > 1e-2
+    assert err < 1e-12

@@ -2,14 +2,12 @@
 reference's voice_conversion (tests/golden/vc_*.npz, made by tests/golden/make_golden_vc.py), plus the properties the
 goldens do not pin: exact invertibility of the forward flow, seeding, the lazily uploaded posterior leaving infer()
 untouched, the 16-bit flow / decoder modes, and the error surface."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from tests import util, vc_input
-from wetts_amd import SynthesizerTrn, _lib, checkpoint, config, synth
+from tests import util
+from wetts_amd import SynthesizerTrn, _lib, config, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -21,32 +19,12 @@ FLOW_TYPE_CASES = ["vc_tiny_b3", "vc_vits2_v1_b2", "vc_tiny_preconv2_spk_b3", "v
                    "vc_tiny_mono_inter_b3"]
 
 
-def _load(name):
-    d = np.load(os.path.join(util.GOLDEN, name + ".npz"))
-    c = {k: d[k] for k in d.files}
-    # the input is rebuilt from its seed (tests/vc_input.py) and held to the sums the fixture recorded of it
-    y = vc_input.make_input([int(v) for v in c["y_lengths"]], int(c["sampling_rate"]), int(c["input_seed"]))
-    assert tuple(y.shape) == tuple(int(v) for v in c["y_shape"])
-    for got, ref in zip(vc_input.input_sums(y), c["y_sums"]):
-        assert abs(got - float(ref)) <= 1e-6 * abs(float(ref)), "rebuilt input differs from the fixture's"
-    c["y"] = y.numpy()
-    if "eps" not in c:  # full-size fixture: the injected draw is regenerated (make_golden_vc.py:vc_noise)
-        B, _, Ty = c["y"].shape
-        I = config.MODEL_CONFIGS[str(c["model"])]["inter_channels"]
-        c["eps"] = np.random.RandomState(int(c["noise_seed"])).standard_normal((B, I, Ty)).astype(np.float32)
-    return c
+_load = util.load_vc_case
 
 
 def _net(case, with_posterior=True):
     mname = str(case["model"])
-    cfg = config.make_config(dict(config.MODEL_CONFIGS[mname]), int(case["n_vocab"]), int(case["n_speakers"]))
-    sd = synth.make_state_dict(cfg, int(case["weight_seed"]))
-    psd = synth.make_posterior_state_dict(cfg, SPEC, int(case["posterior_seed"]))
-    for blob, key in ((checkpoint.pack_blob(cfg, sd), "blob_checksum"),
-                      (checkpoint.pack_posterior_blob(cfg, SPEC, psd), "posterior_checksum")):
-        ref = float(case[key])
-        assert abs(synth.blob_checksum(blob) - ref) <= 1e-6 * max(1.0, abs(ref)), \
-            "synthetic weights differ from the ones the golden vectors were generated with"
+    cfg, sd, psd = util.vc_case_model(case, SPEC)
     net = SynthesizerTrn(int(case["n_vocab"]), SPEC, 32, n_speakers=int(case["n_speakers"]),
                          **config.MODEL_CONFIGS[mname])
     net.load_state_dict(dict(sd, **psd) if with_posterior else sd)

@@ -77,6 +77,45 @@ def case_model(case):
     return cfg, sd, W, blob
 
 
+def load_vc_case(name):
+    """A voice-conversion fixture (tests/golden/vc_*.npz, made by make_golden_vc.py) with its input rebuilt from the
+    seed (tests/vc_input.py, held to the sums the fixture recorded) and, for the full-size case, its injected draw."""
+    from tests import vc_input
+    d = np.load(os.path.join(GOLDEN, name + ".npz"))
+    c = {k: d[k] for k in d.files}
+    y = vc_input.make_input([int(v) for v in c["y_lengths"]], int(c["sampling_rate"]), int(c["input_seed"]))
+    assert tuple(y.shape) == tuple(int(v) for v in c["y_shape"])
+    for got, ref in zip(vc_input.input_sums(y), c["y_sums"]):
+        assert abs(got - float(ref)) <= 1e-6 * abs(float(ref)), "rebuilt input differs from the fixture's"
+    c["y"] = y.numpy()
+    if "eps" not in c:  # full-size fixture: the injected draw is regenerated (make_golden_vc.py:vc_noise)
+        B, _, Ty = c["y"].shape
+        I = config.MODEL_CONFIGS[str(c["model"])]["inter_channels"]
+        c["eps"] = np.random.RandomState(int(c["noise_seed"])).standard_normal((B, I, Ty)).astype(np.float32)
+    return c
+
+
+def vc_weights(cfg, sd, psd, dtype=torch.float32):
+    """The folded weights of a whole model, `enc_q.*` included, as oracle/vits_oracle.py expects them: the float32
+    checkpoint folded in float32 (what the library packs), then widened to `dtype` for a float64 oracle run."""
+    W = checkpoint.fold_weight_norm(dict(sd, **psd))
+    return {k: v.to(dtype) for k, v in W.items()}
+
+
+def vc_case_model(case, spec_channels=513):
+    """(cfg struct, main state_dict, enc_q state_dict) of a voice-conversion fixture, both blob checksums asserted."""
+    cfg = config.make_config(dict(config.MODEL_CONFIGS[str(case["model"])]), int(case["n_vocab"]),
+                             int(case["n_speakers"]))
+    sd = synth.make_state_dict(cfg, int(case["weight_seed"]))
+    psd = synth.make_posterior_state_dict(cfg, spec_channels, int(case["posterior_seed"]))
+    for blob, key in ((checkpoint.pack_blob(cfg, sd), "blob_checksum"),
+                      (checkpoint.pack_posterior_blob(cfg, spec_channels, psd), "posterior_checksum")):
+        ref = float(case[key])
+        assert abs(synth.blob_checksum(blob) - ref) <= 1e-6 * max(1.0, abs(ref)), \
+            "synthetic weights differ from the ones the golden vectors were generated with"
+    return cfg, sd, psd
+
+
 def cfg_dict(cfg):
     """Plain-dict view of wetts_config_t in the shape oracle/vits_oracle.py expects."""
     nk, nd = cfg.n_resblock_kernels, cfg.n_resblock_dilations
