@@ -14,9 +14,15 @@ utterance shard with no collective in the loop (weak scaling).
 `--dump-outputs DIR` writes what the last timed step returned (see dump_outputs); the timed steps draw their noise
 from a generator reseeded when the timed region starts, so the same arguments give the same outputs on every run.
 
-Prints ONE JSON line on rank 0 (see the driver contract).  Extra keys:
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run does only what that line's headline
+needs: set-up, warm-up, the timed steps, the dump if asked, the line.  Extra keys:
   roofline     dominant kernel = the MRF ResBlock conv stack (conv_mfma_kernel), timed live with
-               HIP events recorded on the launch stream inside the timed steps
+               HIP events recorded on the launch stream inside the timed steps; its `traffic` is the
+               committed profiles/ figure
+`--full` also measures, after the timed steps, what takes runs of its own:
+  roofline     `isolated` / `isolated_serial` (extra steps with the pipelining off / the decoder on one
+               stream) and, with --live-traffic auto | 1, a live refresh of `traffic` (two rocprofv3 passes)
+  pcie_inclusive_*  extra steps with H2D of the ids and D2H of the audio
   cpu_baseline the oracle (oracle/vits_oracle.py, a port of the reference running the same ATen
                CPU kernels) timed on this box's host cores on a bounded sample of the workload,
                swept over 1 / 8 / 16 / 32 threads; the best is reported with its thread count
@@ -73,6 +79,10 @@ def parse_args():
     ap.add_argument("--length-scale", type=float, default=0.92,
                     help="calibrated so the synthetic duration heads give 6.0 +- 0.5 frames/phoneme (SURVEY 8d)")
     ap.add_argument("--presteps-s", type=float, default=2.5, help="untimed set-up before the warm-up steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: roofline.isolated / "
+                         "isolated_serial, the PCIe-inclusive rates, the live traffic refresh (--live-traffic) and the "
+                         "CPU baseline (--no-cpu-baseline skips it)")
     ap.add_argument("--cpu-baseline-multi", action="store_true",
                     help="also time the CPU baseline on rank 0 when N > 1 (the contract asks for it at N = 1 only)")
     ap.add_argument("--mas", action="store_true", help="print the monotonic-alignment-search JSON instead")
@@ -87,14 +97,14 @@ def parse_args():
     ap.add_argument("--decoder-serial", action="store_true",
                     help="f32 decoder: the three ResBlock chains of a stage on ONE stream (WETTS_DECODER_SERIAL; the "
                          "form whose kernel trace has non-overlapping per-kernel durations)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (each sub-batch's audio and "
                          "y_mask) as DIR/<name>.npy in float32, at most 64 MB in all (see dump_outputs)")
     ap.add_argument("--live-traffic", default="auto", choices=["auto", "0", "1"],
-                    help="refresh roofline.traffic by running the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of "
-                         "this same command as child processes after the timed region (+ ~1 min).  auto: on for a "
-                         "single-GPU run on a real device that is not itself being profiled; the committed "
+                    help="with --full, refresh roofline.traffic by running the two rocprofv3 --pmc passes (FETCH_SIZE, "
+                         "WRITE_SIZE) of this same command as child processes after the timed region (+ ~1 min).  auto: on "
+                         "for a single-GPU run on a real device that is not itself being profiled; the committed "
                          "profiles/rNN_hbm_traffic.json figure is the fallback and stays in the line beside it")
     ap.add_argument("--cpu-fixture", type=int, default=16,
                     help="also time the oracle on the first N utterances of the batch as ONE padded call (SURVEY 8d's "
@@ -732,9 +742,9 @@ def _bench(args, rank, local_rank, world, mon):
     decoded_frames = frames if decode == "ragged" else padded_frames  # ragged: every row over its own frames
     # In the timed region the dominant class shares the chip with the NEXT step's encoder stages (--overlap 1), so
     # its launches last longer than they do alone.  A few extra steps with the pipelining off give the class's
-    # isolated duration -- kernel quality -- beside the timed region's figure (reported as roofline.isolated).
+    # isolated duration -- kernel quality -- beside the timed region's figure (reported as roofline.isolated; --full).
     iso = None
-    if args.overlap and hasattr(net, "set_overlap"):
+    if args.full and args.overlap and hasattr(net, "set_overlap"):
         net.set_overlap(False)
         be.set_mrf_timing(net, True)
         iso_frames = 0.0
@@ -766,13 +776,15 @@ def _bench(args, rank, local_rank, world, mon):
 
     # PCIe-inclusive variant (SURVEY 8d's wall: H2D of the ids, D2H of the audio; the driver contract
     # says inputs are resident when the timed region starts, so this is reported beside `value`,
-    # never as it): a few extra steps with pinned host buffers on both sides
-    pinned = [tuple(be.pin(t) for t in hb) for hb in host_buckets]
+    # never as it): a few extra steps with pinned host buffers on both sides (--full)
+    pcie_rate = pcie_pipe_rate = 0.0
     n_pcie = max(1, min(3, args.steps))
-    pcie_rate = be.pcie_pass(net, pinned, n_pcie, False, infer_kw)
     n_pipe = max(n_pcie, min(8, args.steps))
-    be.pcie_pass(net, pinned, 1, True, infer_kw)  # allocates the pinned buffers outside the timed pass
-    pcie_pipe_rate = be.pcie_pass(net, pinned, n_pipe, True, infer_kw)
+    if args.full:
+        pinned = [tuple(be.pin(t) for t in hb) for hb in host_buckets]
+        pcie_rate = be.pcie_pass(net, pinned, n_pcie, False, infer_kw)
+        be.pcie_pass(net, pinned, 1, True, infer_kw)  # allocates the pinned buffers outside the timed pass
+        pcie_pipe_rate = be.pcie_pass(net, pinned, n_pipe, True, infer_kw)
 
     # ---- reduce over ranks: time = max, work = sum; every rank's own loop time is gathered for `rank_ms`
     mon.enter("reduce", 100)
@@ -838,7 +850,7 @@ def _bench(args, rank, local_rank, world, mon):
     live_note = {}
 
     def live_wanted():
-        if args.live_traffic == "0" or world != 1 or be.label or not torch.cuda.is_available():
+        if not args.full or args.live_traffic == "0" or world != 1 or be.label or not torch.cuda.is_available():
             return False
         if args.live_traffic == "1":
             return True
@@ -1008,9 +1020,9 @@ def _bench(args, rank, local_rank, world, mon):
         "metric": "audio samples/sec + RTF @22.05 kHz, VITS-Baker, 1/2/4/8 MI355X",
         "value": value,
         # contract (4): inputs are resident in HBM when the timed region starts.  SURVEY 8(d)'s wall -- which includes the
-        # H2D of the ids and the D2H of the audio -- is measured in the same run and printed beside it
+        # H2D of the ids and the D2H of the audio -- is measured in the same --full run and printed beside it
         "value_excludes": "H2D of phoneme ids / D2H of audio (inputs and outputs resident in HBM); the PCIe-inclusive rate "
-                          "of SURVEY 8(d) is `pcie_inclusive_pipelined_samples_per_s`",
+                          "of SURVEY 8(d) is `pcie_inclusive_pipelined_samples_per_s` (--full)",
         "unit": "samples/s", "n_gpus": observed_world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -1046,11 +1058,12 @@ def _bench(args, rank, local_rank, world, mon):
         "ranks_seen": ranks_seen, "blob_checksum_ok": blob_ok,
         "rank_ms": rank_ms, "imbalance": max(rank_ms) / (sum(rank_ms) / len(rank_ms)) - 1.0,
         "plan_slot_imbalance": pl.stats["imbalance"],
-        "pcie_inclusive_samples_per_s": pcie_rate,
-        "pcie_inclusive_pipelined_samples_per_s": pcie_pipe_rate,
-        "pcie_inclusive_note": "ids H2D + infer() + audio D2H per step (SURVEY 8(d)'s wall), reported beside `value`, "
-                               f"never as it.  Serial: blocking copy-out each step ({n_pcie} steps); pipelined: pinned "
-                               f"double buffer, copy-out on its own stream under the next step ({n_pipe} steps)",
+        **({"pcie_inclusive_samples_per_s": pcie_rate,
+            "pcie_inclusive_pipelined_samples_per_s": pcie_pipe_rate,
+            "pcie_inclusive_note": "ids H2D + infer() + audio D2H per step (SURVEY 8(d)'s wall), reported beside `value`, "
+                                   f"never as it.  Serial: blocking copy-out each step ({n_pcie} steps); pipelined: pinned "
+                                   f"double buffer, copy-out on its own stream under the next step ({n_pipe} steps)"}
+           if args.full else {}),
         "roofline": roofline,
     }
     if be.label:
@@ -1059,9 +1072,9 @@ def _bench(args, rank, local_rank, world, mon):
         out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     sharding.diag("result", n_gpus=observed_world, value=value, ms_per_step=out["ms_per_step"], ranks_seen=ranks_seen,
                   rank_ms=rank_ms, imbalance=out["imbalance"], workload=out["config"]["workload"])
-    # contract: the CPU baseline is a rank-0, N = 1 measurement; --cpu-baseline-multi adds it at N > 1 too
+    # contract: the CPU baseline is a rank-0, N = 1 measurement of --full; --cpu-baseline-multi adds it at N > 1 too
     # (rank 0, after the timed region and its barrier; the other ranks wait at the final barrier)
-    if not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_multi):
+    if args.full and not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_multi):
         out["cpu_baseline"] = cpu_baseline(cfg, sd, x, lens, sid, min(args.cpu_sample, total), sr, hop,
                                            args.length_scale, n_fixture=min(args.cpu_fixture, total))
     print(json.dumps(out), file=json_out(), flush=True)

@@ -95,7 +95,7 @@ def test_roofline_fractions_are_fractions_of_what_the_launches_move():
         env.pop("RANK", None)
         env.update(WETTS_BENCH_TEST_BACKEND="tests.bench_stub:StubBackend", PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--phonemes", "16",
-               "--presteps-s", "0.02", "--no-cpu-baseline"] + extra
+               "--presteps-s", "0.02", "--full", "--no-cpu-baseline"] + extra
         p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-3000:]
         d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -111,6 +111,31 @@ def test_roofline_fractions_are_fractions_of_what_the_launches_move():
             assert abs(r["perconv_view"]["ratio_to_hbm_peak"] - 1.2) < 1e-6 and "frac" not in r["perconv_view"]
         bad = {k: v for k, v in fr.items() if v is not None and not (0 <= v <= 1.0)}
         assert not bad, (extra, bad)
+
+
+def test_plain_line_is_the_headline_and_full_adds_the_extra_passes():
+    """A plain `bench.py --steps K --warmup W` runs only what its headline needs; the passes of their own (roofline.isolated,
+    the PCIe-inclusive rates, the CPU baseline) run with --full only.  Both lines carry the same headline keys."""
+    lines = {}
+    for mode in ([], ["--full", "--no-cpu-baseline"]):
+        env = dict(os.environ)
+        env.pop("WORLD_SIZE", None)
+        env.pop("RANK", None)
+        env.update(WETTS_BENCH_TEST_BACKEND="tests.bench_stub:StubBackend", PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2",
+               "--phonemes", "16", "--presteps-s", "0.02"] + mode
+        p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines[bool(mode)] = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    plain, full = lines[False], lines[True]
+    for d in (plain, full):
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "samples/s" and d["higher_is_better"] is True
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f32" and d["roofline"]["frac"] > 0
+    assert {k: plain[k] for k in ("metric", "unit", "dtype")} == {k: full[k] for k in ("metric", "unit", "dtype")}
+    assert not [k for k in plain if k.startswith("pcie_inclusive")] and "cpu_baseline" not in plain
+    assert "isolated" not in plain["roofline"] and "traffic_live" not in plain["roofline"]
+    assert full["pcie_inclusive_samples_per_s"] > 0 and full["pcie_inclusive_pipelined_samples_per_s"] > 0
+    assert full["roofline"]["isolated"]["frac"] > 0 and "cpu_baseline" not in full
 
 
 def test_bench_eight_ranks_aishell3_preset_plan_and_imbalance():
@@ -265,7 +290,7 @@ def test_pmc_traffic_class_sums_and_the_stub_line_never_spawns_a_profiler(tmp_pa
     env.pop("RANK", None)
     env.update(WETTS_BENCH_TEST_BACKEND="tests.bench_stub:StubBackend", PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--phonemes", "16",
-           "--presteps-s", "0.02", "--no-cpu-baseline", "--live-traffic", "1"]
+           "--presteps-s", "0.02", "--full", "--no-cpu-baseline", "--live-traffic", "1"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

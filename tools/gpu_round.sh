@@ -4,6 +4,7 @@
 # Outputs -> gpurun_out/ ; `python tools/summarize_profiles.py r06` copies the judged summaries into profiles/.
 # SKIP_TESTS=1 skips the pytest pass (it is also run by tools/gpu_tests.sh).
 mkdir -p gpurun_out
+OUT=$PWD/$_  # the folder the line above made (absolute: the profiler passes below run elsewhere)
 R=/root/repo
 # the library this pass measures: the digest of its sources (wetts_amd/build.py), stamped into the PMC summary so that
 # bench.py can say whether the committed traffic figure belongs to the library that runs (roofline.traffic_current)
@@ -18,15 +19,15 @@ python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 cd /tmp && export TMPDIR=/tmp
 prof() {  # $1 = tag, rest = bench flags: kernel stats + the two HBM counter passes (separate runs, as the guide prescribes)
   tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_stats_$tag -o r -- python $R/bench.py "$@" --steps 5 --warmup 1 --no-cpu-baseline --live-traffic 0 > $R/gpurun_out/prof_stats_$tag.log 2>&1
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_fetch_$tag -o r -- python $R/bench.py "$@" --steps 1 --warmup 1 --presteps-s 0.3 --no-cpu-baseline --live-traffic 0 > $R/gpurun_out/pmc_fetch_$tag.log 2>&1
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_write_$tag -o r -- python $R/bench.py "$@" --steps 1 --warmup 1 --presteps-s 0.3 --no-cpu-baseline --live-traffic 0 > $R/gpurun_out/pmc_write_$tag.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats_$tag -o r -- python $R/bench.py "$@" --full --steps 5 --warmup 1 --no-cpu-baseline --live-traffic 0 > $OUT/prof_stats_$tag.log 2>&1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch_$tag -o r -- python $R/bench.py "$@" --full --steps 1 --warmup 1 --presteps-s 0.3 --no-cpu-baseline --live-traffic 0 > $OUT/pmc_fetch_$tag.log 2>&1
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write_$tag -o r -- python $R/bench.py "$@" --full --steps 1 --warmup 1 --presteps-s 0.3 --no-cpu-baseline --live-traffic 0 > $OUT/pmc_write_$tag.log 2>&1
   # keep the merged-back scratch small: the per-dispatch traces are not needed once the stats / counter CSVs exist
   find $R/gpurun_out/prof_stats_$tag $R/gpurun_out/pmc_fetch_$tag $R/gpurun_out/pmc_write_$tag -name "*kernel_trace.csv" -delete 2>/dev/null
 }
 prof baker
 # the same line with the stage's chains on ONE stream: per-kernel durations of this trace do not overlap (kernel quality)
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_stats_baker_serial -o r -- python $R/bench.py --decoder-serial --steps 5 --warmup 1 --no-cpu-baseline --live-traffic 0 > $R/gpurun_out/prof_stats_baker_serial.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats_baker_serial -o r -- python $R/bench.py --decoder-serial --full --steps 5 --warmup 1 --no-cpu-baseline --live-traffic 0 > $OUT/prof_stats_baker_serial.log 2>&1
 find $R/gpurun_out/prof_stats_baker_serial -name "*kernel_trace.csv" -delete 2>/dev/null
 prof bf16 --decoder-dtype bf16
 prof cfg2 --config multilingual
@@ -36,18 +37,18 @@ prof vits2vocos --model vits2_vocos_v1
 prof uint8 --decoder-dtype uint8
 cd $R
 python tools/summarize_profiles.py r06 > gpurun_out/traffic_summary.txt 2>&1  # bench.py reads the newest profiles/r*_hbm_traffic.json
-python bench.py --steps 20 --warmup 3 > gpurun_out/bench.json 2> gpurun_out/bench.err
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 cut -c1-420 gpurun_out/bench.json
 python bench.py --gpus 2 --steps 2 --warmup 1 > gpurun_out/bench_gpus2_refused.json 2> gpurun_out/bench_gpus2_refused.err; echo "gpus2 exit=$?" | tee -a gpurun_out/bench_gpus2_refused.err
-WETTS_BENCH_SINGLE_DEVICE=1 WETTS_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_2rank_dryrun.json 2> gpurun_out/bench_2rank_dryrun.err; echo "dryrun exit=$?"
-python bench.py --decoder-serial --steps 20 --warmup 3 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_serial.json 2>/dev/null
-for dt in bf16 f16 uint8; do python bench.py --steps 10 --warmup 3 --no-cpu-baseline --decoder-dtype $dt > gpurun_out/bench_$dt.json 2>/dev/null; done
-python bench.py --config multilingual --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_cfg2_multilingual_bf16.json 2>/dev/null
-python bench.py --config multilingual --decoder-dtype f32 --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_cfg2_multilingual_f32.json 2>/dev/null
-python bench.py --config aishell3 --steps 5 --warmup 2 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_cfg3_aishell3.json 2>/dev/null
-python bench.py --config stress48k --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_cfg4_stress48k_f16.json 2>/dev/null
-python bench.py --model vocos --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_vocos.json 2>/dev/null
-python bench.py --model vits2_vocos_v1 --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > gpurun_out/bench_vits2_vocos.json 2>/dev/null
+WETTS_BENCH_SINGLE_DEVICE=1 WETTS_DIST_BACKEND=gloo python bench.py --gpus 2 --full --steps 3 --warmup 1 --no-cpu-baseline --live-traffic 0 > $OUT/bench_2rank_dryrun.json 2> $OUT/bench_2rank_dryrun.err; echo "dryrun exit=$?"
+python bench.py --decoder-serial --full --steps 20 --warmup 3 --no-cpu-baseline --live-traffic 0 > $OUT/bench_serial.json 2>/dev/null
+for dt in bf16 f16 uint8; do python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --decoder-dtype $dt > $OUT/bench_$dt.json 2>/dev/null; done
+python bench.py --config multilingual --full --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > $OUT/bench_cfg2_multilingual_bf16.json 2>/dev/null
+python bench.py --config multilingual --decoder-dtype f32 --full --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > $OUT/bench_cfg2_multilingual_f32.json 2>/dev/null
+python bench.py --config aishell3 --full --steps 5 --warmup 2 --no-cpu-baseline --live-traffic 0 > $OUT/bench_cfg3_aishell3.json 2>/dev/null
+python bench.py --config stress48k --full --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > $OUT/bench_cfg4_stress48k_f16.json 2>/dev/null
+python bench.py --model vocos --full --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > $OUT/bench_vocos.json 2>/dev/null
+python bench.py --model vits2_vocos_v1 --full --steps 10 --warmup 3 --no-cpu-baseline --live-traffic 0 > $OUT/bench_vits2_vocos.json 2>/dev/null
 python bench.py --stream --model v1 > gpurun_out/stream_v1.json 2>/dev/null
 python bench.py --stream --model vits2_vocos_v1 --stream-cpu > gpurun_out/stream_vits2_vocos.json 2>/dev/null
 python bench.py --mas > gpurun_out/mas.json 2>/dev/null
