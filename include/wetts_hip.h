@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WETTS_ABI_VERSION 10
+#define WETTS_ABI_VERSION 11
 
 #define WETTS_OK 0
 #define WETTS_E_INVALID (-1)   /* bad argument / unsupported configuration */
@@ -374,6 +374,31 @@ int32_t wetts_audio_to_int16(const float* audio, const int64_t* lengths_samples,
  * torch.randn (duration_predictors.py:257) / torch.randn_like (models.py:267).  Element i is a
  * function of (seed, offset, i) only; a draw of n values consumes ceil(n/4) counter steps. */
 int32_t wetts_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+
+/* ---- spectrograms (utils/mel_processing.py, inference side).  Need no model. ------------------------------------- */
+
+/* The window-folded DFT basis of wetts_spectrogram for (n_fft, win): a periodic Hann window of `win` samples centred
+ * in the n_fft frame (torch.stft), built in double on the device and rounded to float once.  numel() gives its size
+ * in floats (-1 for invalid arguments); the caller allocates, builds once and keeps it.  Valid: even n_fft >= 4,
+ * 1 <= win <= n_fft. */
+int64_t wetts_stft_basis_numel(int32_t n_fft, int32_t win);
+int32_t wetts_stft_basis(int32_t n_fft, int32_t win, float* basis, int64_t numel, void* stream);
+
+/* spectrogram_torch (mel_processing.py:43-94), f32: audio [B, L] (row stride L), lengths [B] int64 valid samples per
+ * row (NULL = every row holds L), basis from wetts_stft_basis(n_fft, win).  Each utterance is reflect-padded by
+ * int((n_fft - hop) / 2) at ITS own length, then (center != 0) by n_fft / 2 again, as torch.stft does; spec
+ * [B, n_fft / 2 + 1, T] = sqrt(re^2 + im^2 + 1e-6), frames at or past an utterance's own frame count written as zeros
+ * (and all of them for an utterance too short for the reflect padding, where the reference raises: the caller checks).
+ * Samples past lengths[b] are never read.  Valid: even n_fft >= 4, 1 <= hop <= n_fft, 1 <= win <= n_fft. */
+int32_t wetts_spectrogram(const float* audio, const int64_t* lengths, int32_t B, int64_t L, int32_t n_fft,
+                          int32_t hop, int32_t win, int32_t center, const float* basis, int32_t T, float* spec,
+                          void* stream);
+
+/* spec_to_mel_torch (mel_processing.py:97-111): mel [B, n_mels, T] = log(max(mel_basis @ spec, 1e-5)), spec
+ * [B, n_bins, T], mel_basis [n_mels, n_bins] (librosa.filters.mel; the caller builds it).  frame_lengths [B] int64 may
+ * be NULL; frames at or past it are written as zeros (a zero-padded batch). */
+int32_t wetts_spec_to_mel(const float* spec, const float* mel_basis, const int64_t* frame_lengths, int32_t B,
+                          int32_t n_bins, int32_t n_mels, int32_t T, float* mel, void* stream);
 
 /* out[b,c,t] = x[b,c,t] * mask[b,t]  (`z * y_mask`, models.py:322). */
 int32_t wetts_mask_rows(const float* x, const float* mask, int32_t B, int32_t C, int32_t T,

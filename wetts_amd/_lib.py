@@ -22,7 +22,7 @@ class WettsError(RuntimeError):
     pass
 
 
-ABI_VERSION = 10  # WETTS_ABI_VERSION of include/wetts_hip.h this binding was written against
+ABI_VERSION = 11  # WETTS_ABI_VERSION of include/wetts_hip.h this binding was written against
 
 
 class Config(C.Structure):
@@ -94,6 +94,10 @@ SIGNATURES = {
     "wetts_set_status_word": (_I32, [_P, _P, _P]),
     "wetts_set_seed": (_I32, [_P, C.c_uint64]),
     "wetts_randn": (_I32, [_P, _I64, C.c_uint64, C.c_uint64, _P]),
+    "wetts_stft_basis_numel": (_I64, [_I32, _I32]),
+    "wetts_stft_basis": (_I32, [_I32, _I32, _P, _I64, _P]),
+    "wetts_spectrogram": (_I32, [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "wetts_spec_to_mel": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "wetts_mask_rows": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "wetts_length_regulate": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I64, _F, _I32, _I32, _I32,
                                      _P, _P, _P, _P, _P, _P, _P]),
