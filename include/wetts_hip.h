@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WETTS_ABI_VERSION 11
+#define WETTS_ABI_VERSION 12
 
 #define WETTS_OK 0
 #define WETTS_E_INVALID (-1)   /* bad argument / unsupported configuration */
@@ -51,6 +51,9 @@ extern "C" {
 #define WETTS_STATUS_PHONE_ID_RANGE 2     /* nn.Embedding IndexError, encoders.py:48 */
 #define WETTS_STATUS_SPEAKER_ID_RANGE 4   /* emb_g IndexError, models.py:239 */
 #define WETTS_STATUS_DURATION_NONFINITE 8 /* NaN / inf durations reach .long(), models.py:256 */
+#define WETTS_STATUS_ALIGN_TEXT_LONGER 16 /* some x_lengths[b] > y_lengths[b]: no monotonic alignment exists (the
+                                           * reference's search, monotonic_align.py:22-57, returns a meaningless path) */
+#define WETTS_STATUS_DURATION_NEGATIVE 32 /* a negative frame count given to wetts_counts_to_lengths */
 
 #define WETTS_MAX_STAGES 8
 #define WETTS_MAX_RB_KERNELS 8
@@ -363,6 +366,37 @@ int32_t wetts_flow_forward(const wetts_model_t* m, const float* z, const float* 
 int32_t wetts_mas(const float* neg_cent, const int32_t* t_ys, const int32_t* t_xs, int32_t B,
                   int32_t Ty, int32_t Tx, int32_t* path, void* workspace, int64_t workspace_bytes,
                   void* stream);
+
+/* ---- forced alignment (SynthesizerTrn.forward up to the prior expansion, models.py:171-212, no gradients) ---------- */
+
+/* Alignment scores, models.py:173-184:
+ *   neg_cent[b,t,s] = sum_c ( -1/2 log 2pi - logs_p[b,c,s] - 1/2 (z_p[b,c,t] - m_p[b,c,s])^2 exp(-2 logs_p[b,c,s]) )
+ * as one f32-MFMA GEMM per utterance, [Ty x 2 inter] . [2 inter x Tx], whose operands are built in LDS from
+ *   z_p [B, inter, Ty] (wetts_flow_forward) and stats [B, 2*inter, Tx] (m_p | logs_p, as wetts_text_encoder writes them);
+ * neither operand nor any of the reference's four intermediates is stored.  neg_cent [B, Ty, Tx].  Cells of padded
+ * frames / phonemes hold finite values of no meaning (wetts_mas never reads them as band cells).  inter is the model's. */
+int32_t wetts_align_scores(const wetts_model_t* m, const float* z_p, const float* stats, int32_t B, int32_t Tx,
+                           int32_t Ty, float* neg_cent, void* stream);
+
+/* x_lengths, y_lengths [B] int64 -> t_xs, t_ys [B] int32 clamped to [0, Tx] / [0, Ty]: the per-utterance extents
+ * wetts_mas and wetts_path_to_durations take (the mask sums of monotonic_align.py:16-17).  ORs
+ * WETTS_STATUS_ALIGN_TEXT_LONGER into the registered status word when some utterance has more phonemes than frames. */
+int32_t wetts_align_lengths(const wetts_model_t* m, const int64_t* x_lengths, const int64_t* y_lengths, int32_t B,
+                            int32_t Tx, int32_t Ty, int32_t* t_xs, int32_t* t_ys, void* stream);
+
+/* path -> durations (models.py:196 `w = attn.sum(2)`): path [B,Ty,Tx] int32 0/1 (wetts_mas), t_ys / t_xs int32 [B];
+ *   w [B,Tx] float (exact integers), cum [B,Tx] its inclusive cumsum (what wetts_length_regulate reads),
+ *   frame2phone [B,Ty] int32 the column of the first 1 of each row, -1 for a row without one (the form
+ *   wetts_length_regulate writes), attn [B,Ty,Tx] float (may be NULL) the path as the reference returns it.
+ * Tx <= 16384. */
+int32_t wetts_path_to_durations(const int32_t* path, const int32_t* t_ys, const int32_t* t_xs, int32_t B, int32_t Tx,
+                                int32_t Ty, float* w, float* cum, int32_t* frame2phone, float* attn, void* stream);
+
+/* Given durations -> lengths: the three outputs of wetts_durations_to_lengths from integer frame counts [B,Tx] int64
+ * (w_ceil = counts * x_mask, cum, y_lengths = clamp_min(sum, 1)), with no exp(log(d)) round trip.  A negative count
+ * under the mask ORs WETTS_STATUS_DURATION_NEGATIVE into status_dev (may be NULL) and counts as 0. */
+int32_t wetts_counts_to_lengths(const int64_t* counts, const float* x_mask, int32_t B, int32_t Tx, float* w_ceil,
+                                float* cum, int64_t* y_lengths, int32_t* status_dev, void* stream);
 
 /* a16 inference.py:100-110 output scaling: per utterance peak-normalise to 0.6 full scale,
  * clip, convert to int16.  lengths_samples [B] int64 = valid samples per row (peak is taken

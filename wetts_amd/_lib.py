@@ -22,7 +22,7 @@ class WettsError(RuntimeError):
     pass
 
 
-ABI_VERSION = 11  # WETTS_ABI_VERSION of include/wetts_hip.h this binding was written against
+ABI_VERSION = 12  # WETTS_ABI_VERSION of include/wetts_hip.h this binding was written against
 
 
 class Config(C.Structure):
@@ -119,6 +119,10 @@ SIGNATURES = {
     "wetts_get_istft_mode": (_I32, [_P]),
     "wetts_dynamic_quant_conv1d": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "wetts_mas": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I64, _P]),
+    "wetts_align_scores": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "wetts_align_lengths": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "wetts_path_to_durations": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "wetts_counts_to_lengths": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "wetts_audio_to_int16": (_I32, [_P, _P, _I32, _I64, _P, _P]),
     "wetts_infer_workspace_bytes": (_I64, [_P, _I32, _I32, _I32]),
     "wetts_infer": (_I32, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _I32, _I32, _I32, _P, _P,
@@ -135,6 +139,7 @@ SIGNATURES = {
 
 # WETTS_STATUS_* bits of include/wetts_hip.h
 STATUS_SPLINE_DOMAIN, STATUS_PHONE_ID_RANGE, STATUS_SPEAKER_ID_RANGE, STATUS_DURATION_NONFINITE = 1, 2, 4, 8
+STATUS_ALIGN_TEXT_LONGER, STATUS_DURATION_NEGATIVE = 16, 32
 
 _lib = None
 

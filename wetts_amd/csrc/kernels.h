@@ -179,4 +179,14 @@ int32_t k_mask_rows(const float* x, const float* mask, int B, int C, int T, floa
 int32_t k_mas(const float* neg_cent, const int32_t* t_ys, const int32_t* t_xs, int B, int Ty,
               int Tx, int32_t* path, float* values, hipStream_t s);
 
+// forced alignment (align.hip): scores for the search, lengths in, durations out
+int32_t k_align_scores(const float* z_p, const float* stats, int B, int I, int Tx, int Ty, float* neg_cent,
+                       hipStream_t s);
+int32_t k_align_lengths(const int64_t* x_lengths, const int64_t* y_lengths, int B, int Tx, int Ty, int32_t* t_xs,
+                        int32_t* t_ys, int32_t* status, hipStream_t s);
+int32_t k_path_to_durations(const int32_t* path, const int32_t* t_ys, const int32_t* t_xs, int B, int Tx, int Ty,
+                            float* w, float* cum, int32_t* frame2phone, float* attn, hipStream_t s);
+int32_t k_counts_to_lengths(const int64_t* counts, const float* mask, int B, int T, float* w_ceil, float* cum,
+                            int64_t* y_lengths, int32_t* status, hipStream_t s);
+
 }  // namespace wetts

@@ -3200,6 +3200,34 @@ int32_t wetts_mas(const float* neg_cent, const int32_t* t_ys, const int32_t* t_x
   return k_mas(neg_cent, t_ys, t_xs, B, Ty, Tx, path, (float*)workspace, (hipStream_t)stream);
 }
 
+int32_t wetts_align_scores(const wetts_model_t* m, const float* z_p, const float* stats, int32_t B, int32_t Tx,
+                           int32_t Ty, float* neg_cent, void* stream) {
+  WETTS_REQUIRE(m && z_p && stats && neg_cent, "null argument");
+  WETTS_REQUIRE(B >= 0 && Tx >= 0 && Ty >= 0, "align_scores: negative size");
+  return k_align_scores(z_p, stats, B, m->cfg.inter_channels, Tx, Ty, neg_cent, (hipStream_t)stream);
+}
+
+int32_t wetts_align_lengths(const wetts_model_t* m, const int64_t* x_lengths, const int64_t* y_lengths, int32_t B,
+                            int32_t Tx, int32_t Ty, int32_t* t_xs, int32_t* t_ys, void* stream) {
+  WETTS_REQUIRE(m && x_lengths && y_lengths && t_xs && t_ys, "null argument");
+  WETTS_REQUIRE(B >= 0 && Tx >= 0 && Ty >= 0, "align_lengths: negative size");
+  return k_align_lengths(x_lengths, y_lengths, B, Tx, Ty, t_xs, t_ys, m->status_word, (hipStream_t)stream);
+}
+
+int32_t wetts_path_to_durations(const int32_t* path, const int32_t* t_ys, const int32_t* t_xs, int32_t B, int32_t Tx,
+                                int32_t Ty, float* w, float* cum, int32_t* frame2phone, float* attn, void* stream) {
+  WETTS_REQUIRE(path && t_ys && t_xs && w && cum && frame2phone, "null argument");
+  WETTS_REQUIRE(B >= 0, "path_to_durations: negative size");
+  return k_path_to_durations(path, t_ys, t_xs, B, Tx, Ty, w, cum, frame2phone, attn, (hipStream_t)stream);
+}
+
+int32_t wetts_counts_to_lengths(const int64_t* counts, const float* x_mask, int32_t B, int32_t Tx, float* w_ceil,
+                                float* cum, int64_t* y_lengths, int32_t* status_dev, void* stream) {
+  WETTS_REQUIRE(counts && x_mask && w_ceil && cum && y_lengths, "null argument");
+  WETTS_REQUIRE(B >= 0 && Tx >= 0, "counts_to_lengths: negative size");
+  return k_counts_to_lengths(counts, x_mask, B, Tx, w_ceil, cum, y_lengths, status_dev, (hipStream_t)stream);
+}
+
 int32_t wetts_audio_to_int16(const float* audio, const int64_t* lengths_samples, int32_t B,
                              int64_t L, int16_t* pcm, void* stream) {
   WETTS_REQUIRE(audio && pcm, "null argument");

@@ -5,7 +5,8 @@ there is no eager / CPU fallback anywhere in this module.
 
 Same constructor arguments, same `infer` / `infer_encoder` / `export_*` / `voice_conversion` signatures and
 return tuples as the reference; training (`forward`) is out of scope and raises.  The posterior
-encoder (`enc_q`) is loaded when the checkpoint carries it and runs only inside `voice_conversion`.
+encoder (`enc_q`) is loaded when the checkpoint carries it and runs only inside `voice_conversion` and `align`
+(forced alignment: forward()'s computation up to the expanded prior, models.py:161-212).
 
 Extra, optional keyword arguments (not in the reference): `eps_w` / `eps_z` inject the two
 standard-normal draws the reference makes with torch.randn (duration_predictors.py:257,
@@ -409,6 +410,108 @@ class SynthesizerTrn:
                              g_tgt=g_tgt)
         return o_hat, y_mask.unsqueeze(1), (z, z_p, z_hat)
 
+    # ---- forced alignment (models.py:161-212, the teacher-forced pass up to the expanded prior) -------------------
+    def align(self, x, x_lengths, y, y_lengths, sid=None, eps_q=None):
+        """Which frames of the recording `y` belong to which phoneme of `x`: forward()'s own computation up to
+        models.py:212, without gradients.  x [B,Tx] phoneme ids, y [B, spec_channels, Ty] the spectrogram
+        `posterior_spectrogram` returns, lengths [B].  Returns (attn [B,1,Ty,Tx], w [B,1,Tx], x_mask [B,1,Tx],
+        y_mask [B,1,Ty], (z, z_p, m_p, logs_p, m_q, logs_q)) under forward()'s names and shapes, m_p / logs_p expanded
+        to [B,inter,Ty]; w = attn.sum(2) are the phoneme durations in frames, exact integers.
+
+        Stages, all on the caller's stream: emb_g -> text encoder -> posterior encoder (g) -> forward flow (g) ->
+        alignment scores (models.py:173-184, one MFMA GEMM per utterance) -> monotonic alignment search -> path to
+        durations -> length regulation.  One host read-back per call (the status word).  `eps_q` (optional, not in the
+        reference) injects the posterior draw as in voice_conversion; without it the draw comes from the Philox kernel
+        under torch.manual_seed.  With n_speakers == 0 no sid is needed (g = None), as in forward().
+
+        `use_noise_scaled_mas` (models.py:186-189) anneals noise into the scores during training; this is the
+        deterministic search and ignores it.  An utterance with more phonemes than frames has no monotonic alignment:
+        the reference's search returns a meaningless path for it, here the call raises ValueError.  Ids outside their
+        tables raise IndexError.  `infer(x, x_lengths, sid, durations=w)` resynthesises with the recording's timing."""
+        x = torch.as_tensor(x)
+        y = torch.as_tensor(y)
+        if x.dim() != 2:
+            raise ValueError(f"x must be [B, Tx], got {tuple(x.shape)}")
+        if y.dim() != 3 or y.shape[1] != self.spec_channels or y.shape[0] != x.shape[0]:
+            raise ValueError(f"y must be [{x.shape[0]}, {self.spec_channels}, Ty], got {tuple(y.shape)}")
+        B, Tx = x.shape
+        Ty = y.shape[2]
+        I = self.inter_channels
+        for name, t in (("x_lengths", x_lengths), ("y_lengths", y_lengths)):
+            if tuple(torch.as_tensor(t).shape) != (B,):
+                raise ValueError(f"{name} must be [{B}], got {tuple(torch.as_tensor(t).shape)}")
+        if self.n_speakers > 0 and sid is None:
+            raise ValueError("sid is required when n_speakers > 0")
+        if eps_q is not None and tuple(eps_q.shape) != (B, I, Ty):
+            raise ValueError(f"eps_q must be [{B},{I},{Ty}], got {tuple(eps_q.shape)}")
+        lib = self._require_posterior()
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        x, x_lengths, y, y_lengths = self._ids(x), self._ids(x_lengths), self._f32(y), self._ids(y_lengths)
+        eps_q = self._randn(B, I, Ty) if eps_q is None else self._f32(eps_q)
+        nws = max(int(lib.wetts_workspace_bytes(self._handle, B, Tx, 0)),
+                  int(lib.wetts_posterior_workspace_bytes(self._handle, B, Ty)),
+                  int(lib.wetts_workspace_bytes(self._handle, B, 0, Ty)))
+        ws = (self._ws_dec if self.overlap else self._ws).get(nws, dev)  # as voice_conversion: the side stream owns _ws
+        s = _lib.current_stream_ptr()
+        H = self.hidden_channels
+        g_buf = torch.empty(B, max(1, self.gin_channels), **f32)
+        g = g_buf if self.n_speakers > 0 else None
+        x_enc, stats, x_mask = torch.empty(B, H, Tx, **f32), torch.empty(B, 2 * I, Tx, **f32), torch.empty(B, Tx, **f32)
+        t_xs, t_ys = torch.empty(B, **i32), torch.empty(B, **i32)
+        status = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.wetts_set_status_word(self._handle, _lib.ptr(status), s), "set_status_word")
+        try:
+            _lib.check(lib.wetts_speaker_embedding(self._handle, _lib.ptr(self._ids(sid)) if g is not None else None, B,
+                                                   _lib.ptr(g_buf), s), "speaker_embedding")
+            _lib.check(lib.wetts_text_encoder(self._handle, _lib.ptr(x), _lib.ptr(x_lengths), _lib.ptr(g), B, Tx,
+                                              _lib.ptr(x_enc), _lib.ptr(stats), _lib.ptr(x_mask), _lib.ptr(ws), nws, s),
+                       "text_encoder")
+            _lib.check(lib.wetts_align_lengths(self._handle, _lib.ptr(x_lengths), _lib.ptr(y_lengths), B, Tx, Ty,
+                                               _lib.ptr(t_xs), _lib.ptr(t_ys), s), "align_lengths")
+        finally:
+            lib.wetts_set_status_word(self._handle, None, s)
+        z, m_q, logs_q = (torch.empty(B, I, Ty, **f32) for _ in range(3))
+        y_mask = torch.empty(B, Ty, **f32)
+        _lib.check(lib.wetts_posterior_encoder(self._handle, _lib.ptr(y), _lib.ptr(y_lengths), _lib.ptr(g),
+                                               _lib.ptr(eps_q), B, Ty, _lib.ptr(z), _lib.ptr(m_q), _lib.ptr(logs_q),
+                                               _lib.ptr(y_mask), _lib.ptr(ws), nws, s), "posterior_encoder")
+        z_p = self._flow_pass(z, y_mask, g, False, ws, nws)
+        # caller-owned, as in monotonic_align.maximum_path: the scores, the search's value table and the int32 path
+        neg_cent = torch.empty(B, Ty, Tx, **f32)
+        values = torch.empty(max(1, B * Ty * Tx), **f32)
+        path = torch.empty(B, Ty, Tx, **i32)
+        _lib.check(lib.wetts_align_scores(self._handle, _lib.ptr(z_p), _lib.ptr(stats), B, Tx, Ty, _lib.ptr(neg_cent), s),
+                   "align_scores")
+        _lib.check(lib.wetts_mas(_lib.ptr(neg_cent), _lib.ptr(t_ys), _lib.ptr(t_xs), B, Ty, Tx, _lib.ptr(path),
+                                 _lib.ptr(values), values.numel() * 4, s), "wetts_mas")
+        w, cum = torch.empty(B, Tx, **f32), torch.empty(B, Tx, **f32)
+        f2p = torch.empty(B, Ty, **i32)
+        attn = torch.empty(B, Ty, Tx, **f32)
+        _lib.check(lib.wetts_path_to_durations(_lib.ptr(path), _lib.ptr(t_ys), _lib.ptr(t_xs), B, Tx, Ty, _lib.ptr(w),
+                                               _lib.ptr(cum), _lib.ptr(f2p), _lib.ptr(attn), s), "path_to_durations")
+        # models.py:209-212 through the kernel infer() expands the prior with: noise_scale = 0, its z_p output unused
+        m_p, logs_p, unused = (torch.empty(B, I, Ty, **f32) for _ in range(3))
+        f2p_lr, y_mask_lr = torch.empty(B, Ty, **i32), torch.empty(B, Ty, **f32)
+        _lib.check(lib.wetts_length_regulate(self._handle, _lib.ptr(stats), _lib.ptr(cum), _lib.ptr(x_mask),
+                                             _lib.ptr(y_lengths), _lib.ptr(z_p), I * Ty, Ty, 0.0, B, Tx, Ty,
+                                             _lib.ptr(f2p_lr), _lib.ptr(y_mask_lr), None, _lib.ptr(m_p),
+                                             _lib.ptr(logs_p), _lib.ptr(unused), s), "length_regulate")
+        self.last_status = int(status.cpu().item()) & 0xFFFFFFFF  # the call's one host sync
+        if self.last_status & _lib.STATUS_PHONE_ID_RANGE:
+            raise IndexError("index out of range in self (phoneme id outside emb, encoders.py:48)")
+        if self.last_status & _lib.STATUS_SPEAKER_ID_RANGE:
+            raise IndexError("index out of range in self (sid outside emb_g, models.py:163)")
+        if self.last_status & _lib.STATUS_ALIGN_TEXT_LONGER:
+            raise ValueError("align: an utterance has more phonemes than frames (x_lengths[b] > y_lengths[b]); no "
+                             "monotonic alignment exists")
+        self._last_align = dict(g=g, x_enc=x_enc, stats=stats, x_mask=x_mask, y_mask=y_mask, z=z, m_q=m_q, logs_q=logs_q,
+                                z_p=z_p, neg_cent=neg_cent, path=path, t_xs=t_xs, t_ys=t_ys, w=w, cum=cum,
+                                frame2phone=f2p, attn=attn, m_p=m_p, logs_p=logs_p)
+        return (attn.unsqueeze(1), w.unsqueeze(1), x_mask.unsqueeze(1), y_mask.unsqueeze(1),
+                (z, z_p, m_p, logs_p, m_q, logs_q))
+
     # ---- stages ----------------------------------------------------------------------------------
     def _ids(self, t):
         return t.to(device=self.device, dtype=torch.int64).contiguous()
@@ -430,12 +533,14 @@ class SynthesizerTrn:
                                                _lib.current_stream_ptr()), "speaker_embedding")
         return g if self.n_speakers > 0 else None
 
-    def _encode(self, x, x_lengths, sid, noise_scale, length_scale, noise_scale_w, eps_w, eps_z):
+    def _encode(self, x, x_lengths, sid, noise_scale, length_scale, noise_scale_w, eps_w, eps_z, durations=None):
         """Everything of infer() up to and including flow^-1 (== infer_encoder, models.py:282-331).
         Returns a dict of stage tensors."""
         lib = self._require()
         x = self._ids(x)
         x_lengths = self._ids(x_lengths)
+        if durations is not None:
+            return self._encode_stages_given(lib, x, x_lengths, sid, noise_scale, self._ids(durations), eps_z)
         return self._encode_stages(lib, x, x_lengths, sid, noise_scale, length_scale, noise_scale_w, eps_w, eps_z)
 
     def _randn(self, *shape):
@@ -508,6 +613,49 @@ class SynthesizerTrn:
                                                       status_ptr, s), "durations_to_lengths")
         finally:
             lib.wetts_set_status_word(self._handle, None, s)
+
+    def _launch_pre_given(self, lib, pb, counts):
+        """_launch_pre with the duration predictor replaced by the caller's frame counts [B,Tx] int64."""
+        B, Tx = pb["B"], pb["Tx"]
+        s = _lib.current_stream_ptr()
+        status_ptr = C.c_void_p(pb["meta"].data_ptr() + 8 * B)
+        _lib.check(lib.wetts_set_status_word(self._handle, status_ptr, s), "set_status_word")
+        try:
+            g = pb["g"] if self.n_speakers > 0 else None
+            _lib.check(lib.wetts_speaker_embedding(self._handle, _lib.ptr(pb["sid"]) if self.n_speakers > 0 else None, B,
+                                                   _lib.ptr(pb["g"]), s), "speaker_embedding")
+            _lib.check(lib.wetts_text_encoder(self._handle, _lib.ptr(pb["x"]), _lib.ptr(pb["x_lengths"]), _lib.ptr(g), B,
+                                              Tx, _lib.ptr(pb["x_enc"]), _lib.ptr(pb["stats"]), _lib.ptr(pb["x_mask"]),
+                                              _lib.ptr(pb["ws"]), pb["nws"], s), "text_encoder")
+            _lib.check(lib.wetts_counts_to_lengths(_lib.ptr(counts), _lib.ptr(pb["x_mask"]), B, Tx, _lib.ptr(pb["w_ceil"]),
+                                                   _lib.ptr(pb["cum"]), _lib.ptr(pb["meta"]), status_ptr, s),
+                       "counts_to_lengths")
+        finally:
+            lib.wetts_set_status_word(self._handle, None, s)
+
+    def _encode_stages_given(self, lib, x, x_lengths, sid, noise_scale, counts, eps_z):
+        """_encode_stages for infer(durations=): no duration predictor and no eps_w draw; everything behind the
+        y_lengths read-back is _encode_stages' own second half."""
+        B, Tx = x.shape
+        I = self.inter_channels
+        if self.n_speakers > 0 and sid is None:
+            raise ValueError("sid is required when n_speakers > 0")
+        pb = self._pre_buffers(B, Tx)
+        pb["x"], pb["x_lengths"] = x, x_lengths
+        if self.n_speakers > 0:
+            pb["sid"] = self._ids(sid)
+        pb["ws"], pb["nws"] = self._workspace(B, Tx, 0)
+        self._launch_pre_given(lib, pb, counts)
+        y_host, Ty = self._read_lengths(pb)
+        if self.last_status & _lib.STATUS_DURATION_NEGATIVE:
+            raise ValueError("durations must not be negative")
+        qb = self._post_buffers(B, Tx, Ty)
+        qb["eps_z"] = self._randn(B, I, Ty) if eps_z is None else self._f32(eps_z)
+        if tuple(qb["eps_z"].shape) != (B, I, Ty):
+            raise ValueError(f"eps_z must be [{B},{I},{Ty}], got {tuple(qb['eps_z'].shape)}")
+        qb["ws"], qb["nws"] = self._workspace(B, Tx, Ty)
+        self._launch_post(lib, pb, qb, noise_scale)
+        return self._stage_dict(pb, qb, y_host, Ty)
 
     def _read_lengths(self, pb):
         """The one host sync of infer(): y_lengths and the status word in one D2H copy (the output length is data
@@ -618,15 +766,24 @@ class SynthesizerTrn:
 
     # ---- the reference's public inference API ----------------------------------------------------
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1.0,
-              max_len=None, eps_w=None, eps_z=None, ragged=False):
+              max_len=None, eps_w=None, eps_z=None, ragged=False, durations=None):
         """models.py:228-280.  Returns (o [B,1,Ty*hop], attn [B,1,Ty,Tx], y_mask [B,1,Ty],
         (z, z_p, m_p, logs_p) [B,inter,Ty]); z is unmasked, as in the reference.
+
+        `durations` (not in the reference): frames per phoneme, an integer tensor [B,Tx] or [B,1,Tx] (a float tensor
+        of whole numbers such as align()'s `w` is converted), masked by x_lengths.  The duration predictor is then
+        skipped and these counts are w_ceil; `length_scale`, `noise_scale_w` and `eps_w` are ignored.  Everything
+        behind the y_lengths read-back is unchanged.  A negative count raises ValueError.
 
         `ragged=True` (not in the reference): the generator has no masks, so the reference decodes every row of a
         padded batch to the longest utterance; ragged decodes row b over its own y_lengths[b] frames -- the audio
         the reference returns when that utterance is synthesised alone (its CLI's call shape) -- and writes zeros
         behind it.  The masked stages (encoder, durations, flow) are batch independent either way."""
-        st = self._encode_ordered(x, x_lengths, sid, noise_scale, length_scale, noise_scale_w, eps_w, eps_z)
+        if durations is not None:
+            durations = self._check_durations(x, durations)
+            st = self._encode_ordered(x, x_lengths, sid, noise_scale, 1.0, 1.0, None, eps_z, durations=durations)
+        else:
+            st = self._encode_ordered(x, x_lengths, sid, noise_scale, length_scale, noise_scale_w, eps_w, eps_z)
         Ty = st["Ty"]
         L = Ty if max_len is None else max(0, min(Ty, int(max_len)))
         o = self._decode(st["z"], st["g"], st["y_mask"], L, st["y_lengths"] if ragged else None)
@@ -634,7 +791,20 @@ class SynthesizerTrn:
         return (o, st["attn"].unsqueeze(1), st["y_mask"].unsqueeze(1),
                 (st["z"], st["z_p"], st["m_p"], st["logs_p"]))
 
-    def _encode_ordered(self, x, x_lengths, sid, noise_scale, length_scale, noise_scale_w, eps_w, eps_z):
+    @staticmethod
+    def _check_durations(x, durations):
+        """infer(durations=) argument check, before anything is launched: -> [B,Tx] tensor."""
+        d = torch.as_tensor(durations)
+        B, Tx = tuple(torch.as_tensor(x).shape)
+        if d.dim() == 3 and d.shape[1] == 1:
+            d = d[:, 0]
+        if tuple(d.shape) != (B, Tx):
+            raise ValueError(f"durations must be [{B},{Tx}] or [{B},1,{Tx}], got {tuple(torch.as_tensor(durations).shape)}")
+        if d.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise ValueError(f"durations must be an integer tensor, got {d.dtype}")
+        return d
+
+    def _encode_ordered(self, x, x_lengths, sid, noise_scale, length_scale, noise_scale_w, eps_w, eps_z, durations=None):
         """_encode for the public entry points (infer, infer_encoder, export_encoder_forward, the sessions): on the
         caller's stream, or -- overlap mode -- on the side stream with the result ordered in front of whatever the
         caller's stream does next.  EVERY entry point goes through here, so in overlap mode the encoder workspace
@@ -644,12 +814,12 @@ class SynthesizerTrn:
         drained, and raises if a device op that produces them was still pending (it serialises the pipeline: debug only)."""
         if not (self.overlap and self.device.type == "cuda"):
             return self._encode(x, x_lengths, sid, float(noise_scale), float(length_scale),
-                                float(noise_scale_w), eps_w, eps_z)
+                                float(noise_scale_w), eps_w, eps_z, durations)
         main = torch.cuda.current_stream(self.device)
         if self._enc_stream is None:
             self._enc_stream = self._new_enc_stream()
         if self._debug_overlap:
-            ins = [t for t in (x, x_lengths, sid, eps_w, eps_z) if isinstance(t, torch.Tensor) and t.is_cuda]
+            ins = [t for t in (x, x_lengths, sid, eps_w, eps_z, durations) if isinstance(t, torch.Tensor) and t.is_cuda]
             with torch.cuda.stream(self._enc_stream):
                 seen = [t.clone() for t in ins]  # what the side stream reads at this point of the caller's stream
             main.synchronize()
@@ -663,7 +833,7 @@ class SynthesizerTrn:
                         "or call set_overlap(False).")
         with torch.cuda.stream(self._enc_stream):
             st = self._encode(x, x_lengths, sid, float(noise_scale), float(length_scale),
-                              float(noise_scale_w), eps_w, eps_z)
+                              float(noise_scale_w), eps_w, eps_z, durations)
             done = torch.cuda.Event()
             done.record(self._enc_stream)
         main.wait_event(done)
