@@ -33,6 +33,9 @@ struct TensorSpec {
   std::string name;
   int64_t shape[4];
   int64_t offset, numel;
+  // a conv weight's geometry beyond its shape (add_conv); never exported (wetts_blob_tensor_info)
+  int dil = 1, pad = 0, transposed = 0, up = 0;
+  int bias = -1;  // index of `prefix.bias` in the layout, -1: none
 };
 
 struct Layout {
@@ -49,7 +52,28 @@ struct Layout {
     index[name] = (int)specs.size();
     specs.push_back(t);
   }
+  // `prefix`.weight [Cout][Cin][k] ([Cin][Cout][k] for a ConvTranspose1d) and then `prefix`.bias [Cout]
+  void add_conv(const std::string& prefix, int Cout, int Cin, int k, int dil = 1, int pad = 0, int transposed = 0,
+                int up = 0, bool bias = true) {
+    const int w = (int)specs.size();
+    add(prefix + ".weight", transposed ? Cin : Cout, transposed ? Cout : Cin, k);
+    specs[w].dil = dil; specs[w].pad = pad; specs[w].transposed = transposed; specs[w].up = up;
+    if (bias) {
+      specs[w].bias = w + 1;
+      add(prefix + ".bias", Cout);
+    }
+  }
+  const TensorSpec* find(const std::string& name) const {
+    auto it = index.find(name);
+    return it == index.end() ? nullptr : &specs[it->second];
+  }
 };
+
+// the tensor `name` of the blob laid out by L, or null when L has none of that name
+static const float* tensor(const Layout& L, const float* blob, const std::string& name) {
+  const TensorSpec* t = L.find(name);
+  return t ? blob + t->offset : nullptr;
+}
 
 static std::string S(const char* fmt, ...) {
   char buf[256];
@@ -118,32 +142,44 @@ static bool mono_flows(const wetts_config_t* c) { return c->transformer_flows >=
 static int flow_key_stride(const wetts_config_t* c) { return mono_flows(c) ? 3 : 2; }
 // the flow types whose Encoder runs on the I/2 channels of x0 (2 layers, 2 heads, window_size=None, FFN kernel 3)
 static bool half_enc_flows(const wetts_config_t* c) { return c->transformer_flows == 1 || mono_flows(c); }
-// that Encoder's tensors under `p`.pre_transformer (flows.py:111-119 and :256-264 build the same module)
-static void add_half_encoder(Layout& L, const std::string& p, int Hh) {
-  for (int l = 0; l < 2; ++l) {
-    std::string a = p + S(".pre_transformer.attn_layers.%d", l);
-    for (const char* n : {"conv_q", "conv_k", "conv_v", "conv_o"}) {
-      L.add(a + "." + n + ".weight", Hh, Hh, 1);
-      L.add(a + "." + n + ".bias", Hh);
-    }
-    L.add(p + S(".pre_transformer.norm_layers_1.%d.gamma", l), Hh);
-    L.add(p + S(".pre_transformer.norm_layers_1.%d.beta", l), Hh);
-    std::string ff = p + S(".pre_transformer.ffn_layers.%d", l);
-    L.add(ff + ".conv_1.weight", Hh, Hh, 3);
-    L.add(ff + ".conv_1.bias", Hh);
-    L.add(ff + ".conv_2.weight", Hh, Hh, 3);
-    L.add(ff + ".conv_2.bias", Hh);
-    L.add(p + S(".pre_transformer.norm_layers_2.%d.gamma", l), Hh);
-    L.add(p + S(".pre_transformer.norm_layers_2.%d.beta", l), Hh);
+
+// layer l of an attentions.Encoder under `p`: H channels, FFN width F and kernel k; window >= 0 (not None): with the
+// relative-position embeddings of a head of dk channels.  FFN _same_padding: pad_l = (k-1)//2 (attentions.py:422-429)
+static void add_enc_layer(Layout& L, const std::string& p, int l, int H, int F, int k, int window = -1, int dk = 0) {
+  const std::string a = p + S(".attn_layers.%d", l), f = p + S(".ffn_layers.%d", l);
+  if (window >= 0) {
+    L.add(a + ".emb_rel_k", 1, 2 * window + 1, dk);
+    L.add(a + ".emb_rel_v", 1, 2 * window + 1, dk);
   }
+  for (const char* n : {"conv_q", "conv_k", "conv_v", "conv_o"}) L.add_conv(a + "." + n, H, H, 1);
+  L.add(p + S(".norm_layers_1.%d.gamma", l), H);
+  L.add(p + S(".norm_layers_1.%d.beta", l), H);
+  L.add_conv(f + ".conv_1", F, H, k, 1, (k - 1) / 2);
+  L.add_conv(f + ".conv_2", H, F, k, 1, (k - 1) / 2);
+  L.add(p + S(".norm_layers_2.%d.gamma", l), H);
+  L.add(p + S(".norm_layers_2.%d.beta", l), H);
+}
+
+// Encoder(half, half, n_heads=2, n_layers=2, kernel_size=3, window_size=None) under `p`.pre_transformer (flows.py:111-119
+// and :256-264 build the same module)
+static void add_half_encoder(Layout& L, const std::string& p, int Hh) {
+  for (int l = 0; l < 2; ++l) add_enc_layer(L, p + ".pre_transformer", l, Hh, Hh, 3);
+}
+
+// modules.WN under `p`: in_layers (dilation_rate 1 => dilation 1, padding (k-1)/2), res_skip_layers, cond_layer
+static void add_wn(Layout& L, const std::string& p, int H, int k, int n_layers, int gin) {
+  for (int i = 0; i < n_layers; ++i) {
+    L.add_conv(p + S(".in_layers.%d", i), 2 * H, H, k, 1, (k - 1) / 2);
+    L.add_conv(p + S(".res_skip_layers.%d", i), i < n_layers - 1 ? 2 * H : H, H, 1);
+  }
+  if (gin > 0) L.add_conv(p + ".cond_layer", 2 * H * n_layers, gin, 1);
 }
 
 static void add_dds(Layout& L, const std::string& p, int C, int k, int n) {
   for (int i = 0; i < n; ++i) {
     L.add(p + S(".convs_sep.%d.weight", i), C, 1, k);
     L.add(p + S(".convs_sep.%d.bias", i), C);
-    L.add(p + S(".convs_1x1.%d.weight", i), C, C, 1);
-    L.add(p + S(".convs_1x1.%d.bias", i), C);
+    L.add_conv(p + S(".convs_1x1.%d", i), C, C, 1);
     L.add(p + S(".norms_1.%d.gamma", i), C);
     L.add(p + S(".norms_1.%d.beta", i), C);
     L.add(p + S(".norms_2.%d.gamma", i), C);
@@ -151,134 +187,106 @@ static void add_dds(Layout& L, const std::string& p, int C, int k, int n) {
   }
 }
 
+// One conv of the HiFi-GAN generator (decoders.py:15-88), in checkpoint order
+struct GenConv {
+  enum Kind { PRE, UP, C1, C2, POST, COND } kind;
+  int i, n, d;         // stage, ResBlock (i * n_kernels + j) and dilation index, where the kind has them
+  std::string prefix;  // `prefix`.weight / .bias
+  int Cout, Cin, k, dil, pad, up;
+};
+
+// ResBlock1 has convs1 (dilated) + convs2 per dilation, ResBlock2 only `convs` (C1)
+static std::vector<GenConv> hifigan_convs(const wetts_config_t* c) {
+  std::vector<GenConv> v;
+  int ch = c->upsample_initial_channel;
+  v.push_back({GenConv::PRE, 0, 0, 0, "dec.conv_pre", ch, c->inter_channels, 7, 1, 3, 0});
+  for (int i = 0; i < c->n_upsamples; ++i) {
+    const int u = c->upsample_rates[i], uk = c->upsample_kernel_sizes[i];
+    v.push_back({GenConv::UP, i, 0, 0, S("dec.ups.%d", i), ch / 2, ch, uk, 1, (uk - u) / 2, u});
+    ch /= 2;
+    for (int j = 0; j < c->n_resblock_kernels; ++j) {
+      const int n = i * c->n_resblock_kernels + j, k = c->resblock_kernel_sizes[j];
+      for (int d = 0; d < c->n_resblock_dilations; ++d) {
+        const int dil = c->resblock_dilation_sizes[j][d];
+        const int pad = (k * dil - dil) / 2;  // get_padding, commons.py:13-14
+        if (c->resblock == 1) {
+          v.push_back({GenConv::C1, i, n, d, S("dec.resblocks.%d.convs1.%d", n, d), ch, ch, k, dil, pad, 0});
+          v.push_back({GenConv::C2, i, n, d, S("dec.resblocks.%d.convs2.%d", n, d), ch, ch, k, 1, (k - 1) / 2, 0});
+        } else {
+          v.push_back({GenConv::C1, i, n, d, S("dec.resblocks.%d.convs.%d", n, d), ch, ch, k, dil, pad, 0});
+        }
+      }
+    }
+  }
+  v.push_back({GenConv::POST, 0, 0, 0, "dec.conv_post", 1, ch, 7, 1, 3, 0});  // bias=False (decoders.py:59)
+  if (has_g(c)) v.push_back({GenConv::COND, 0, 0, 0, "dec.cond", c->upsample_initial_channel, c->gin_channels, 1, 1, 0, 0});
+  return v;
+}
+
 static void build_layout(const wetts_config_t* c, Layout& L) {
   const int H = c->hidden_channels, I = c->inter_channels, F = c->filter_channels;
-  const int dk = H / c->n_heads, W = 2 * c->window_size + 1, gin = c->gin_channels;
+  const int gin = c->gin_channels, fk = c->flow_kernel_size;
   L.add("enc_p.emb.weight", c->n_vocab, H);
-  for (int l = 0; l < c->n_layers; ++l) {
-    std::string a = S("enc_p.encoder.attn_layers.%d", l);
-    L.add(a + ".emb_rel_k", 1, W, dk);
-    L.add(a + ".emb_rel_v", 1, W, dk);
-    for (const char* n : {"conv_q", "conv_k", "conv_v", "conv_o"}) {
-      L.add(a + "." + n + ".weight", H, H, 1);
-      L.add(a + "." + n + ".bias", H);
-    }
-    L.add(S("enc_p.encoder.norm_layers_1.%d.gamma", l), H);
-    L.add(S("enc_p.encoder.norm_layers_1.%d.beta", l), H);
-    std::string f = S("enc_p.encoder.ffn_layers.%d", l);
-    L.add(f + ".conv_1.weight", F, H, c->kernel_size);
-    L.add(f + ".conv_1.bias", F);
-    L.add(f + ".conv_2.weight", H, F, c->kernel_size);
-    L.add(f + ".conv_2.bias", H);
-    L.add(S("enc_p.encoder.norm_layers_2.%d.gamma", l), H);
-    L.add(S("enc_p.encoder.norm_layers_2.%d.beta", l), H);
-  }
+  for (int l = 0; l < c->n_layers; ++l)
+    add_enc_layer(L, "enc_p.encoder", l, H, F, c->kernel_size, c->window_size, H / c->n_heads);
   if (c->use_spk_conditioned_encoder) {  // nn.Linear(gin, hidden) (attentions.py:41-43)
     L.add("enc_p.encoder.spk_emb_linear.weight", H, gin);
     L.add("enc_p.encoder.spk_emb_linear.bias", H);
   }
-  L.add("enc_p.proj.weight", 2 * I, H, 1);
-  L.add("enc_p.proj.bias", 2 * I);
+  L.add_conv("enc_p.proj", 2 * I, H, 1);
   if (has_g(c)) L.add("emb_g.weight", c->n_speakers, gin);
 
   if (c->use_sdp) {
     // StochasticDurationPredictor(hidden, 192, 3, 0.5, 4): filter_channels := in_channels
     // (duration_predictors.py:166); only the tensors the reverse branch touches.
     const int C = H;
-    L.add("dp.pre.weight", C, H, 1);
-    L.add("dp.pre.bias", C);
-    L.add("dp.proj.weight", C, C, 1);
-    L.add("dp.proj.bias", C);
+    L.add_conv("dp.pre", C, H, 1);
+    L.add_conv("dp.proj", C, C, 1);
     add_dds(L, "dp.convs", C, 3, 3);
-    if (has_g(c)) {
-      L.add("dp.cond.weight", C, gin, 1);
-      L.add("dp.cond.bias", C);
-    }
+    if (has_g(c)) L.add_conv("dp.cond", C, gin, 1);
     L.add("dp.flows.0.m", 2, 1);
     L.add("dp.flows.0.logs", 2, 1);
     // flows = [EA, CF1, Flip, CF2, Flip, ...]; reverse drops CF1 (duration_predictors.py:255-256)
     for (int f = 1; f < c->sdp_n_flows; ++f) {
       std::string p = S("dp.flows.%d", 2 * f + 1);
-      L.add(p + ".pre.weight", C, 1, 1);
-      L.add(p + ".pre.bias", C);
+      L.add_conv(p + ".pre", C, 1, 1);
       add_dds(L, p + ".convs", C, 3, 3);
-      L.add(p + ".proj.weight", 29, C, 1);
-      L.add(p + ".proj.bias", 29);
+      L.add_conv(p + ".proj", 29, C, 1);
     }
   } else {
     const int Fd = c->dp_filter_channels;
-    L.add("dp.conv_1.weight", Fd, H, 3);
-    L.add("dp.conv_1.bias", Fd);
+    L.add_conv("dp.conv_1", Fd, H, 3, 1, 1);
     L.add("dp.norm_1.gamma", Fd);
     L.add("dp.norm_1.beta", Fd);
-    L.add("dp.conv_2.weight", Fd, Fd, 3);
-    L.add("dp.conv_2.bias", Fd);
+    L.add_conv("dp.conv_2", Fd, Fd, 3, 1, 1);
     L.add("dp.norm_2.gamma", Fd);
     L.add("dp.norm_2.beta", Fd);
-    L.add("dp.proj.weight", 1, Fd, 1);
-    L.add("dp.proj.bias", 1);
-    if (has_g(c)) {
-      L.add("dp.cond.weight", H, gin, 1);
-      L.add("dp.cond.bias", H);
-    }
+    L.add_conv("dp.proj", 1, Fd, 1);
+    if (has_g(c)) L.add_conv("dp.cond", H, gin, 1);
   }
 
   for (int f = 0; f < c->flow_n_flows; ++f) {
     std::string p = S("flow.flows.%d", flow_key_stride(c) * f);
     // Encoder(half, half, n_heads=2, n_layers=2, kernel_size=3, window_size=None), flows.py:111-119
     if (c->transformer_flows == 1) add_half_encoder(L, p, I / 2);
-    if (c->transformer_flows == 2) {
-      // Encoder(hidden, hidden, n_heads=2, n_layers=1, kernel_size=flow kernel, window 4), flows.py:40-48
-      const int dkf = H / 2, Wf = 2 * 4 + 1, fk2 = c->flow_kernel_size;
-      std::string a = p + ".pre_transformer.attn_layers.0";
-      L.add(a + ".emb_rel_k", 1, Wf, dkf);
-      L.add(a + ".emb_rel_v", 1, Wf, dkf);
-      for (const char* n : {"conv_q", "conv_k", "conv_v", "conv_o"}) {
-        L.add(a + "." + n + ".weight", H, H, 1);
-        L.add(a + "." + n + ".bias", H);
-      }
-      L.add(p + ".pre_transformer.norm_layers_1.0.gamma", H);
-      L.add(p + ".pre_transformer.norm_layers_1.0.beta", H);
-      L.add(p + ".pre_transformer.ffn_layers.0.conv_1.weight", H, H, fk2);
-      L.add(p + ".pre_transformer.ffn_layers.0.conv_1.bias", H);
-      L.add(p + ".pre_transformer.ffn_layers.0.conv_2.weight", H, H, fk2);
-      L.add(p + ".pre_transformer.ffn_layers.0.conv_2.bias", H);
-      L.add(p + ".pre_transformer.norm_layers_2.0.gamma", H);
-      L.add(p + ".pre_transformer.norm_layers_2.0.beta", H);
-    }
-    L.add(p + ".pre.weight", H, I / 2, 1);
-    L.add(p + ".pre.bias", H);
-    for (int i = 0; i < c->flow_wn_layers; ++i) {
-      L.add(p + S(".enc.in_layers.%d.weight", i), 2 * H, H, c->flow_kernel_size);
-      L.add(p + S(".enc.in_layers.%d.bias", i), 2 * H);
-      int rs = (i < c->flow_wn_layers - 1) ? 2 * H : H;
-      L.add(p + S(".enc.res_skip_layers.%d.weight", i), rs, H, 1);
-      L.add(p + S(".enc.res_skip_layers.%d.bias", i), rs);
-    }
-    if (has_g(c)) {
-      L.add(p + ".enc.cond_layer.weight", 2 * H * c->flow_wn_layers, gin, 1);
-      L.add(p + ".enc.cond_layer.bias", 2 * H * c->flow_wn_layers);
-    }
-    L.add(p + ".post.weight", I / 2, H, 1);
-    L.add(p + ".post.bias", I / 2);
+    // Encoder(hidden, hidden, n_heads=2, n_layers=1, kernel_size=flow kernel, window 4), flows.py:40-48
+    if (c->transformer_flows == 2) add_enc_layer(L, p + ".pre_transformer", 0, H, H, fk, 4, H / 2);
+    L.add_conv(p + ".pre", H, I / 2, 1);
+    add_wn(L, p + ".enc", H, fk, c->flow_wn_layers, has_g(c) ? gin : 0);
+    L.add_conv(p + ".post", I / 2, H, 1);
     if (mono_flows(c)) {
       // MonoTransformerFlowLayer(channels, hidden, mean_only=True): pre_transformer + post 1x1 on I/2 channels
       // (flows.py:242-269)
       std::string q = S("flow.flows.%d", 3 * f + 2);
       add_half_encoder(L, q, I / 2);
-      L.add(q + ".post.weight", I / 2, I / 2, 1);
-      L.add(q + ".post.bias", I / 2);
+      L.add_conv(q + ".post", I / 2, I / 2, 1);
     }
   }
 
   if (c->vocoder_type == 1) {  // VocosGenerator (decoders.py:251-284)
     const int VC = c->vocos_channels, VH = c->vocos_h_channels, VO = c->istft_n_fft + 2;
-    L.add("dec.in_conv.weight", VC, I, 1);
-    L.add("dec.in_conv.bias", VC);
-    if (has_g(c)) {
-      L.add("dec.cond.weight", VC, gin, 1);
-      L.add("dec.cond.bias", VC);
-    }
+    L.add_conv("dec.in_conv", VC, I, 1);
+    if (has_g(c)) L.add_conv("dec.cond", VC, gin, 1);
     L.add("dec.norm_pre.gamma", VC);
     L.add("dec.norm_pre.beta", VC);
     for (int l = 0; l < c->vocos_num_layers; ++l) {
@@ -287,47 +295,17 @@ static void build_layout(const wetts_config_t* c, Layout& L) {
       L.add(p + ".dw_conv.bias", VC);
       L.add(p + ".norm.gamma", VC);
       L.add(p + ".norm.beta", VC);
-      L.add(p + ".pw_conv1.weight", VH, VC, 1);
-      L.add(p + ".pw_conv1.bias", VH);
-      L.add(p + ".pw_conv2.weight", VC, VH, 1);
-      L.add(p + ".pw_conv2.bias", VC);
+      L.add_conv(p + ".pw_conv1", VH, VC, 1);
+      L.add_conv(p + ".pw_conv2", VC, VH, 1);
       L.add(p + ".scale", 1, VC, 1);
     }
     L.add("dec.norm_post.gamma", VC);
     L.add("dec.norm_post.beta", VC);
-    L.add("dec.out_conv.weight", VO, VC, 1);
-    L.add("dec.out_conv.bias", VO);
+    L.add_conv("dec.out_conv", VO, VC, 1);
     return;
   }
-  const int C0 = c->upsample_initial_channel;
-  L.add("dec.conv_pre.weight", C0, I, 7);
-  L.add("dec.conv_pre.bias", C0);
-  int ch = C0;
-  for (int i = 0; i < c->n_upsamples; ++i) {
-    L.add(S("dec.ups.%d.weight", i), ch, ch / 2, c->upsample_kernel_sizes[i]);
-    L.add(S("dec.ups.%d.bias", i), ch / 2);
-    ch /= 2;
-    for (int j = 0; j < c->n_resblock_kernels; ++j) {
-      int n = i * c->n_resblock_kernels + j;
-      int k = c->resblock_kernel_sizes[j];
-      for (int d = 0; d < c->n_resblock_dilations; ++d) {
-        if (c->resblock == 1) {
-          L.add(S("dec.resblocks.%d.convs1.%d.weight", n, d), ch, ch, k);
-          L.add(S("dec.resblocks.%d.convs1.%d.bias", n, d), ch);
-          L.add(S("dec.resblocks.%d.convs2.%d.weight", n, d), ch, ch, k);
-          L.add(S("dec.resblocks.%d.convs2.%d.bias", n, d), ch);
-        } else {
-          L.add(S("dec.resblocks.%d.convs.%d.weight", n, d), ch, ch, k);
-          L.add(S("dec.resblocks.%d.convs.%d.bias", n, d), ch);
-        }
-      }
-    }
-  }
-  L.add("dec.conv_post.weight", 1, ch, 7);
-  if (has_g(c)) {
-    L.add("dec.cond.weight", C0, gin, 1);
-    L.add("dec.cond.bias", C0);
-  }
+  for (const GenConv& g : hifigan_convs(c))
+    L.add_conv(g.prefix, g.Cout, g.Cin, g.k, g.dil, g.pad, g.kind == GenConv::UP, g.up, g.kind != GenConv::POST);
 }
 
 // PosteriorEncoder(spec_channels, inter, hidden, 5, 1, 16, gin_channels) (models.py:125-133, encoders.py:60-99): the
@@ -336,21 +314,10 @@ constexpr int kPostLayers = 16, kPostKernel = 5;
 
 static void build_posterior_layout(const wetts_config_t* c, int spec, Layout& L) {
   const int H = c->hidden_channels, I = c->inter_channels;
-  L.add("enc_q.pre.weight", H, spec, 1);
-  L.add("enc_q.pre.bias", H);
-  for (int i = 0; i < kPostLayers; ++i) {
-    L.add(S("enc_q.enc.in_layers.%d.weight", i), 2 * H, H, kPostKernel);
-    L.add(S("enc_q.enc.in_layers.%d.bias", i), 2 * H);
-    const int rs = (i < kPostLayers - 1) ? 2 * H : H;
-    L.add(S("enc_q.enc.res_skip_layers.%d.weight", i), rs, H, 1);
-    L.add(S("enc_q.enc.res_skip_layers.%d.bias", i), rs);
-  }
-  if (c->gin_channels > 0) {  // WN builds cond_layer whenever gin_channels != 0 (modules.py:35-36)
-    L.add("enc_q.enc.cond_layer.weight", 2 * H * kPostLayers, c->gin_channels, 1);
-    L.add("enc_q.enc.cond_layer.bias", 2 * H * kPostLayers);
-  }
-  L.add("enc_q.proj.weight", 2 * I, H, 1);
-  L.add("enc_q.proj.bias", 2 * I);
+  L.add_conv("enc_q.pre", H, spec, 1);
+  // WN builds cond_layer whenever gin_channels != 0 (modules.py:35-36)
+  add_wn(L, "enc_q.enc", H, kPostKernel, kPostLayers, c->gin_channels);
+  L.add_conv("enc_q.proj", 2 * I, H, 1);
 }
 
 static int validate_posterior(const wetts_config_t* c, int spec) {
@@ -447,9 +414,6 @@ struct wetts_model {
   // output) -- what bench.py prices the HBM roofline of the fused 16-bit classes with, instead of SURVEY 8(d)'s
   // per-conv figure, which counts planes a fused launch never moves
   mutable double mrf_bytes = 0;
-  // MRF chains: the n_k ResBlocks of a stage are independent until their sum, so they run on
-  // separate HIP streams (forked from / joined to the caller's stream with events); one chain's
-  // launch tail and prologue/epilogue phases overlap another chain's MFMA work.
   // bf16 decoder (opt-in, wetts_set_decoder_precision): weights packed by the setter
   mutable int dec_precision = 0;  // 0 = f32, 1 = bf16, 2 = f16
   mutable int dec_unfused = 0;    // diagnostic: run ResBlock1 pairs as two conv launches
@@ -510,6 +474,9 @@ struct wetts_model {
   int wn_fuse = 1;      // WETTS_TUNE wn_fuse: the f32 flow's residual / skip update in the res_skip conv's epilogue (1: small launches, 2: always, 0: wn_update_kernel)
   int small_fork = 1;   // WETTS_TUNE small_fork: the chains of a small (streaming-window) stage on their own streams
   int conv_groups = 1;  // WETTS_TUNE conv_groups: independent single convs of a ResBlock1 step in one launch (0: one each)
+  // MRF chains: the n_k ResBlocks of a stage are independent until their sum, so they run on
+  // separate HIP streams (forked from / joined to the caller's stream with events); one chain's
+  // launch tail and prologue/epilogue phases overlap another chain's MFMA work.
   hipStream_t aux_stream[WETTS_MAX_RB_KERNELS] = {};
   hipEvent_t ev_fork = nullptr, ev_chain[WETTS_MAX_RB_KERNELS] = {};
   bool fork_ok = false;  // every handle above exists (else: the serial grouped schedule)
@@ -525,11 +492,7 @@ struct wetts_model {
   std::vector<PackedConv> pe_in, pe_rs, fwd_pre;
   const float *pe_cond_w = nullptr, *pe_cond_b = nullptr;
 
-  const float* T(const std::string& name) const {
-    auto it = layout.index.find(name);
-    if (it == layout.index.end()) return nullptr;
-    return blob + layout.specs[it->second].offset;
-  }
+  const float* T(const std::string& name) const { return tensor(layout, blob, name); }
 };
 
 namespace wetts {
@@ -552,33 +515,88 @@ struct Bump {
   }
 };
 
-static int32_t pack(wetts_model* m, const std::string& wname, const std::string& bname, int Cout,
-                    int Cin, int k, int dil, int pad, int transposed, int up, hipStream_t s,
-                    PackedConv* pc, int rev_in = 0, int gate_H = 0) {
-  const float* w = m->T(wname);
-  WETTS_REQUIRE(w != nullptr, "tensor %s missing from layout", wname.c_str());
-  const float* b = bname.empty() ? nullptr : m->T(bname);
-  WETTS_TRY(pack_conv_weight(w, b, Cout, Cin, k, dil, pad, transposed, up, s, pc, rev_in, gate_H));
+// A conv of the layout by name: its tensors in `blob` and the geometry add_conv recorded
+struct ConvRef {
+  const float *w, *b;
+  int Cout, Cin, k, dil, pad, transposed, up;
+};
+
+static int32_t find_conv(const Layout& L, const float* blob, const std::string& prefix, ConvRef* r) {
+  const std::string wname = prefix + ".weight";
+  const TensorSpec* t = L.find(wname);
+  WETTS_REQUIRE(t != nullptr, "tensor %s missing from layout", wname.c_str());
+  r->w = blob + t->offset;
+  r->b = t->bias >= 0 ? blob + L.specs[t->bias].offset : nullptr;
+  r->Cout = (int)t->shape[t->transposed ? 1 : 0];
+  r->Cin = (int)t->shape[t->transposed ? 0 : 1];
+  r->k = (int)t->shape[2];
+  r->dil = t->dil; r->pad = t->pad; r->transposed = t->transposed; r->up = t->up;
+  return WETTS_OK;
+}
+
+// The conv `prefix` of layout L packed for the f32 / 16-bit / uint8 conv kernels.  The caller owns *pc.
+static int32_t pack(const Layout& L, const float* blob, const std::string& prefix, hipStream_t s, PackedConv* pc,
+                    int rev_in = 0, int gate_H = 0) {
+  ConvRef r;
+  WETTS_TRY(find_conv(L, blob, prefix, &r));
+  return pack_conv_weight(r.w, r.b, r.Cout, r.Cin, r.k, r.dil, r.pad, r.transposed, r.up, s, pc, rev_in, gate_H);
+}
+
+static int32_t pack16(const Layout& L, const float* blob, const std::string& prefix, int f16, hipStream_t s,
+                      PackedConvB* pc, int gate_h = 0) {
+  ConvRef r;
+  WETTS_TRY(find_conv(L, blob, prefix, &r));
+  return pack_conv_weight_bf16(r.w, r.b, r.Cout, r.Cin, r.k, r.dil, r.pad, r.transposed, r.up, f16, s, pc, gate_h);
+}
+
+static int32_t packq(const Layout& L, const float* blob, const std::string& prefix, hipStream_t s, PackedQConv* pc) {
+  ConvRef r;
+  WETTS_TRY(find_conv(L, blob, prefix, &r));
+  return pack_qconv_weight(r.w, r.b, r.Cout, r.Cin, r.k, r.dil, r.pad, s, pc);
+}
+
+// The n layers of the WN under `p` (`p`.in_layers.i, its gate rows interleaved for gate_H > 0, and `p`.res_skip_layers.i)
+// at f32 into in32 / rs32, or, where those are null, at 16 bit (f16: half, else bf16) into in16 / rs16
+static int32_t pack_wn(const Layout& L, const float* blob, const std::string& p, int n, int gate_H, hipStream_t s,
+                       std::vector<PackedConv>* in32, std::vector<PackedConv>* rs32,
+                       std::vector<PackedConvB>* in16 = nullptr, std::vector<PackedConvB>* rs16 = nullptr, int f16 = 0) {
+  for (int i = 0; i < n; ++i) {
+    const std::string in = p + S(".in_layers.%d", i), rs = p + S(".res_skip_layers.%d", i);
+    if (in32) {
+      WETTS_TRY(pack(L, blob, in, s, &(*in32)[i], 0, gate_H));
+      WETTS_TRY(pack(L, blob, rs, s, &(*rs32)[i]));
+    } else {
+      WETTS_TRY(pack16(L, blob, in, f16, s, &(*in16)[i], gate_H));
+      WETTS_TRY(pack16(L, blob, rs, f16, s, &(*rs16)[i]));
+    }
+  }
+  return WETTS_OK;
+}
+
+// a conv of the main blob, freed with the model (all_packed)
+static int32_t load_conv(wetts_model* m, const std::string& prefix, hipStream_t s, PackedConv* pc, int rev_in = 0,
+                         int gate_H = 0) {
+  WETTS_TRY(pack(m->layout, m->blob, prefix, s, pc, rev_in, gate_H));
   m->all_packed.push_back(pc);
   return WETTS_OK;
 }
 
 // conv_q, conv_k, conv_v of a MultiHeadAttention (attentions.py:225-233) as ONE 1x1 conv with
 // 3*H output channels: the three weights / biases are concatenated into an owned device buffer
-static int32_t pack_qkv(wetts_model* m, const std::string& a, int H, hipStream_t s, PackedConv* pc) {
+static int32_t pack_qkv(wetts_model* m, const std::string& a, hipStream_t s, PackedConv* pc) {
+  const char* names[3] = {"conv_q", "conv_k", "conv_v"};
+  ConvRef r[3];
+  for (int i = 0; i < 3; ++i) WETTS_TRY(find_conv(m->layout, m->blob, a + "." + names[i], &r[i]));
+  const int H = r[0].Cout;
   float *w = nullptr, *b = nullptr;
   WETTS_HIP_CHECK(hipMalloc((void**)&w, (size_t)3 * H * H * sizeof(float)));
   m->v_owned.push_back(w);
   WETTS_HIP_CHECK(hipMalloc((void**)&b, (size_t)3 * H * sizeof(float)));
   m->v_owned.push_back(b);
-  const char* names[3] = {"conv_q", "conv_k", "conv_v"};
   for (int i = 0; i < 3; ++i) {
-    const float* wi = m->T(a + "." + names[i] + ".weight");
-    const float* bi = m->T(a + "." + names[i] + ".bias");
-    WETTS_REQUIRE(wi && bi, "tensor %s.%s missing from layout", a.c_str(), names[i]);
-    WETTS_HIP_CHECK(hipMemcpyAsync(w + (size_t)i * H * H, wi, (size_t)H * H * sizeof(float),
+    WETTS_HIP_CHECK(hipMemcpyAsync(w + (size_t)i * H * H, r[i].w, (size_t)H * H * sizeof(float),
                                    hipMemcpyDeviceToDevice, s));
-    WETTS_HIP_CHECK(hipMemcpyAsync(b + (size_t)i * H, bi, (size_t)H * sizeof(float),
+    WETTS_HIP_CHECK(hipMemcpyAsync(b + (size_t)i * H, r[i].b, (size_t)H * sizeof(float),
                                    hipMemcpyDeviceToDevice, s));
   }
   WETTS_TRY(pack_conv_weight(w, b, 3 * H, H, 1, 1, 0, 0, 0, s, pc));
@@ -586,7 +604,23 @@ static int32_t pack_qkv(wetts_model* m, const std::string& a, int H, hipStream_t
   return WETTS_OK;
 }
 
-static int32_t load_dds(wetts_model* m, const std::string& p, int C, hipStream_t s, DDS* d) {
+// layer l of the Encoder under `p` (add_enc_layer); rel_k / rel_v stay null where it has no emb_rel_* (window_size=None)
+static int32_t load_enc_layer(wetts_model* m, const std::string& p, int l, hipStream_t s, EncLayer* e) {
+  const std::string a = p + S(".attn_layers.%d", l), f = p + S(".ffn_layers.%d", l);
+  e->rel_k = m->T(a + ".emb_rel_k");
+  e->rel_v = m->T(a + ".emb_rel_v");
+  WETTS_TRY(pack_qkv(m, a, s, &e->qkv));
+  WETTS_TRY(load_conv(m, a + ".conv_o", s, &e->o));
+  e->n1g = m->T(p + S(".norm_layers_1.%d.gamma", l));
+  e->n1b = m->T(p + S(".norm_layers_1.%d.beta", l));
+  e->n2g = m->T(p + S(".norm_layers_2.%d.gamma", l));
+  e->n2b = m->T(p + S(".norm_layers_2.%d.beta", l));
+  WETTS_TRY(load_conv(m, f + ".conv_1", s, &e->f1));
+  WETTS_TRY(load_conv(m, f + ".conv_2", s, &e->f2));
+  return WETTS_OK;
+}
+
+static int32_t load_dds(wetts_model* m, const std::string& p, hipStream_t s, DDS* d) {
   for (int i = 0; i < 3; ++i) {
     d->sep_w[i] = m->T(p + S(".convs_sep.%d.weight", i));
     d->sep_b[i] = m->T(p + S(".convs_sep.%d.bias", i));
@@ -594,8 +628,7 @@ static int32_t load_dds(wetts_model* m, const std::string& p, int C, hipStream_t
     d->n1b[i] = m->T(p + S(".norms_1.%d.beta", i));
     d->n2g[i] = m->T(p + S(".norms_2.%d.gamma", i));
     d->n2b[i] = m->T(p + S(".norms_2.%d.beta", i));
-    WETTS_TRY(pack(m, p + S(".convs_1x1.%d.weight", i), p + S(".convs_1x1.%d.bias", i), C, C, 1, 1,
-                   0, 0, 0, s, &d->c1x1[i]));
+    WETTS_TRY(load_conv(m, p + S(".convs_1x1.%d", i), s, &d->c1x1[i]));
   }
   return WETTS_OK;
 }
@@ -605,9 +638,9 @@ static int32_t load_dds(wetts_model* m, const std::string& p, int C, hipStream_t
 // iSTFT head expressed as one more 1x1 conv whose weight is the windowed inverse-rDFT basis.
 static int32_t build_vocos(wetts_model* m, hipStream_t s) {
   const wetts_config_t* c = &m->cfg;
-  const int I = c->inter_channels, VC = c->vocos_channels, VH = c->vocos_h_channels;
+  const int VC = c->vocos_channels, VH = c->vocos_h_channels;
   const int NF = c->istft_n_fft, VO = NF + 2;
-  WETTS_TRY(pack(m, "dec.in_conv.weight", "dec.in_conv.bias", VC, I, 1, 1, 0, 0, 0, s, &m->v_in));
+  WETTS_TRY(load_conv(m, "dec.in_conv", s, &m->v_in));
   m->dec_cond_w = m->T("dec.cond.weight");
   m->dec_cond_b = m->T("dec.cond.bias");
   m->v_npre_g = m->T("dec.norm_pre.gamma");
@@ -622,7 +655,7 @@ static int32_t build_vocos(wetts_model* m, hipStream_t s) {
     cn.dw_b = m->T(p + ".dw_conv.bias");
     cn.ng = m->T(p + ".norm.gamma");
     cn.nb = m->T(p + ".norm.beta");
-    WETTS_TRY(pack(m, p + ".pw_conv1.weight", p + ".pw_conv1.bias", VH, VC, 1, 1, 0, 0, 0, s, &cn.pw1));
+    WETTS_TRY(load_conv(m, p + ".pw_conv1", s, &cn.pw1));
     const float* w2 = m->T(p + ".pw_conv2.weight");
     const float* b2 = m->T(p + ".pw_conv2.bias");
     const float* sc = m->T(p + ".scale");
@@ -637,7 +670,7 @@ static int32_t build_vocos(wetts_model* m, hipStream_t s) {
     WETTS_TRY(pack_conv_weight(w2s, b2s, VC, VH, 1, 1, 0, 0, 0, s, &cn.pw2));
     m->all_packed.push_back(&cn.pw2);
   }
-  WETTS_TRY(pack(m, "dec.out_conv.weight", "dec.out_conv.bias", VO, VC, 1, 1, 0, 0, 0, s, &m->v_out));
+  WETTS_TRY(load_conv(m, "dec.out_conv", s, &m->v_out));
   float* basis = nullptr;
   WETTS_HIP_CHECK(hipMalloc((void**)&basis, (size_t)NF * VO * sizeof(float)));
   m->v_owned.push_back(basis);
@@ -658,40 +691,20 @@ static int32_t build_vocos(wetts_model* m, hipStream_t s) {
 
 static int32_t build_model(wetts_model* m, hipStream_t s) {
   const wetts_config_t* c = &m->cfg;
-  const int H = c->hidden_channels, I = c->inter_channels, F = c->filter_channels;
-  const int ks = c->kernel_size;
   m->emb = m->T("enc_p.emb.weight");
   m->enc_spk_w = m->T("enc_p.encoder.spk_emb_linear.weight");
   m->enc_spk_b = m->T("enc_p.encoder.spk_emb_linear.bias");
   m->enc.resize(c->n_layers);
-  for (int l = 0; l < c->n_layers; ++l) {
-    EncLayer& e = m->enc[l];
-    std::string a = S("enc_p.encoder.attn_layers.%d", l);
-    e.rel_k = m->T(a + ".emb_rel_k");
-    e.rel_v = m->T(a + ".emb_rel_v");
-    WETTS_TRY(pack_qkv(m, a, H, s, &e.qkv));
-    WETTS_TRY(pack(m, a + ".conv_o.weight", a + ".conv_o.bias", H, H, 1, 1, 0, 0, 0, s, &e.o));
-    e.n1g = m->T(S("enc_p.encoder.norm_layers_1.%d.gamma", l));
-    e.n1b = m->T(S("enc_p.encoder.norm_layers_1.%d.beta", l));
-    e.n2g = m->T(S("enc_p.encoder.norm_layers_2.%d.gamma", l));
-    e.n2b = m->T(S("enc_p.encoder.norm_layers_2.%d.beta", l));
-    std::string f = S("enc_p.encoder.ffn_layers.%d", l);
-    // FFN _same_padding: pad_l = (k-1)//2, pad_r = k//2 (attentions.py:422-429)
-    WETTS_TRY(pack(m, f + ".conv_1.weight", f + ".conv_1.bias", F, H, ks, 1, (ks - 1) / 2, 0, 0, s,
-                   &e.f1));
-    WETTS_TRY(pack(m, f + ".conv_2.weight", f + ".conv_2.bias", H, F, ks, 1, (ks - 1) / 2, 0, 0, s,
-                   &e.f2));
-  }
-  WETTS_TRY(pack(m, "enc_p.proj.weight", "enc_p.proj.bias", 2 * I, H, 1, 1, 0, 0, 0, s,
-                 &m->enc_proj));
+  for (int l = 0; l < c->n_layers; ++l) WETTS_TRY(load_enc_layer(m, "enc_p.encoder", l, s, &m->enc[l]));
+  WETTS_TRY(load_conv(m, "enc_p.proj", s, &m->enc_proj));
   m->emb_g = m->T("emb_g.weight");
 
   m->dp_cond_w = m->T("dp.cond.weight");
   m->dp_cond_b = m->T("dp.cond.bias");
   if (c->use_sdp) {
-    WETTS_TRY(pack(m, "dp.pre.weight", "dp.pre.bias", H, H, 1, 1, 0, 0, 0, s, &m->sdp_pre));
-    WETTS_TRY(pack(m, "dp.proj.weight", "dp.proj.bias", H, H, 1, 1, 0, 0, 0, s, &m->sdp_proj));
-    WETTS_TRY(load_dds(m, "dp.convs", H, s, &m->sdp_dds));
+    WETTS_TRY(load_conv(m, "dp.pre", s, &m->sdp_pre));
+    WETTS_TRY(load_conv(m, "dp.proj", s, &m->sdp_proj));
+    WETTS_TRY(load_dds(m, "dp.convs", s, &m->sdp_dds));
     m->ea_m = m->T("dp.flows.0.m");
     m->ea_logs = m->T("dp.flows.0.logs");
     m->cflows.resize(c->sdp_n_flows - 1);
@@ -700,14 +713,13 @@ static int32_t build_model(wetts_model* m, hipStream_t s) {
       std::string p = S("dp.flows.%d", 2 * f + 1);
       cf.pre_w = m->T(p + ".pre.weight");
       cf.pre_b = m->T(p + ".pre.bias");
-      WETTS_TRY(load_dds(m, p + ".convs", H, s, &cf.dds));
-      WETTS_TRY(pack(m, p + ".proj.weight", p + ".proj.bias", 29, H, 1, 1, 0, 0, 0, s, &cf.proj));
+      WETTS_TRY(load_dds(m, p + ".convs", s, &cf.dds));
+      WETTS_TRY(load_conv(m, p + ".proj", s, &cf.proj));
     }
   } else {
-    const int Fd = c->dp_filter_channels;
-    WETTS_TRY(pack(m, "dp.conv_1.weight", "dp.conv_1.bias", Fd, H, 3, 1, 1, 0, 0, s, &m->dp_c1));
-    WETTS_TRY(pack(m, "dp.conv_2.weight", "dp.conv_2.bias", Fd, Fd, 3, 1, 1, 0, 0, s, &m->dp_c2));
-    WETTS_TRY(pack(m, "dp.proj.weight", "dp.proj.bias", 1, Fd, 1, 1, 0, 0, 0, s, &m->dp_proj));
+    WETTS_TRY(load_conv(m, "dp.conv_1", s, &m->dp_c1));
+    WETTS_TRY(load_conv(m, "dp.conv_2", s, &m->dp_c2));
+    WETTS_TRY(load_conv(m, "dp.proj", s, &m->dp_proj));
     m->dp_n1g = m->T("dp.norm_1.gamma");
     m->dp_n1b = m->T("dp.norm_1.beta");
     m->dp_n2g = m->T("dp.norm_2.gamma");
@@ -717,115 +729,57 @@ static int32_t build_model(wetts_model* m, hipStream_t s) {
   m->flows.resize(c->flow_n_flows);
   for (int f = 0; f < c->flow_n_flows; ++f) {
     FlowW& fw = m->flows[f];
-    std::string p = S("flow.flows.%d", flow_key_stride(c) * f);
+    const std::string p = S("flow.flows.%d", flow_key_stride(c) * f);
     // plain coupling layers read x0 = Flip(x)[:I/2] = x[I-1 .. I/2]: the Flip is folded into `pre` by packing
     // its input channels in reverse, so the conv reads channels I/2 .. I-1 in place (no index arithmetic
     // while staging); the pre_conv transformer flow materialises x0 and keeps the natural order
-    WETTS_TRY(pack(m, p + ".pre.weight", p + ".pre.bias", H, I / 2, 1, 1, 0, 0, 0, s, &fw.pre,
-                   c->transformer_flows == 1 ? 0 : 1));
-    WETTS_TRY(pack(m, p + ".post.weight", p + ".post.bias", I / 2, H, 1, 1, 0, 0, 0, s, &fw.post));
+    WETTS_TRY(load_conv(m, p + ".pre", s, &fw.pre, c->transformer_flows == 1 ? 0 : 1));
+    WETTS_TRY(load_conv(m, p + ".post", s, &fw.post));
     fw.in_layers.resize(c->flow_wn_layers);
     fw.res_skip.resize(c->flow_wn_layers);
-    const int fk = c->flow_kernel_size;
-    for (int i = 0; i < c->flow_wn_layers; ++i) {
-      // WN dilation_rate = 1 (models.py:133-138) => dilation 1**i = 1, padding (k-1)/2
-      // rows interleaved (tanh row i, sigmoid row H + i): the gate runs in the conv's epilogue (OUT_GATE, common.h)
-      WETTS_TRY(pack(m, p + S(".enc.in_layers.%d.weight", i), p + S(".enc.in_layers.%d.bias", i),
-                     2 * H, H, fk, 1, (fk - 1) / 2, 0, 0, s, &fw.in_layers[i], 0, H));
-      int rs = (i < c->flow_wn_layers - 1) ? 2 * H : H;
-      WETTS_TRY(pack(m, p + S(".enc.res_skip_layers.%d.weight", i),
-                     p + S(".enc.res_skip_layers.%d.bias", i), rs, H, 1, 1, 0, 0, 0, s,
-                     &fw.res_skip[i]));
-    }
+    for (auto* v : {&fw.in_layers, &fw.res_skip})
+      for (PackedConv& pc : *v) m->all_packed.push_back(&pc);
+    // in_layers rows interleaved (tanh row i, sigmoid row H + i): the gate runs in the conv's epilogue (OUT_GATE, common.h)
+    WETTS_TRY(pack_wn(m->layout, m->blob, p + ".enc", c->flow_wn_layers, c->hidden_channels, s, &fw.in_layers,
+                      &fw.res_skip));
     fw.cond_w = m->T(p + ".enc.cond_layer.weight");
     fw.cond_b = m->T(p + ".enc.cond_layer.bias");
     if (c->transformer_flows == 2) {
       fw.pre_tr.resize(1);
-      EncLayer& e = fw.pre_tr[0];
-      std::string a = p + ".pre_transformer.attn_layers.0";
-      e.rel_k = m->T(a + ".emb_rel_k");
-      e.rel_v = m->T(a + ".emb_rel_v");
-      WETTS_TRY(pack_qkv(m, a, H, s, &e.qkv));
-      WETTS_TRY(pack(m, a + ".conv_o.weight", a + ".conv_o.bias", H, H, 1, 1, 0, 0, 0, s, &e.o));
-      e.n1g = m->T(p + ".pre_transformer.norm_layers_1.0.gamma");
-      e.n1b = m->T(p + ".pre_transformer.norm_layers_1.0.beta");
-      e.n2g = m->T(p + ".pre_transformer.norm_layers_2.0.gamma");
-      e.n2b = m->T(p + ".pre_transformer.norm_layers_2.0.beta");
-      std::string ff = p + ".pre_transformer.ffn_layers.0";
-      WETTS_TRY(pack(m, ff + ".conv_1.weight", ff + ".conv_1.bias", H, H, fk, 1, (fk - 1) / 2, 0, 0, s, &e.f1));
-      WETTS_TRY(pack(m, ff + ".conv_2.weight", ff + ".conv_2.bias", H, H, fk, 1, (fk - 1) / 2, 0, 0, s, &e.f2));
-    }
-    if (mono_flows(c)) {
-      const std::string q = S("flow.flows.%d", 3 * f + 2);
-      WETTS_TRY(pack(m, q + ".post.weight", q + ".post.bias", I / 2, I / 2, 1, 1, 0, 0, 0, s, &fw.mono_post));
+      WETTS_TRY(load_enc_layer(m, p + ".pre_transformer", 0, s, &fw.pre_tr[0]));
     }
     if (half_enc_flows(c)) {
-      const int Hh = I / 2;
+      const std::string q = mono_flows(c) ? S("flow.flows.%d", 3 * f + 2) : p;
+      if (mono_flows(c)) WETTS_TRY(load_conv(m, q + ".post", s, &fw.mono_post));
       std::vector<EncLayer>& tr = mono_flows(c) ? fw.mono_tr : fw.pre_tr;
-      if (mono_flows(c)) p = S("flow.flows.%d", 3 * f + 2);
       tr.resize(2);
-      for (int l = 0; l < 2; ++l) {
-        EncLayer& e = tr[l];
-        std::string a = p + S(".pre_transformer.attn_layers.%d", l);
-        e.rel_k = e.rel_v = nullptr;  // window_size=None
-        WETTS_TRY(pack_qkv(m, a, Hh, s, &e.qkv));
-        WETTS_TRY(pack(m, a + ".conv_o.weight", a + ".conv_o.bias", Hh, Hh, 1, 1, 0, 0, 0, s, &e.o));
-        e.n1g = m->T(p + S(".pre_transformer.norm_layers_1.%d.gamma", l));
-        e.n1b = m->T(p + S(".pre_transformer.norm_layers_1.%d.beta", l));
-        e.n2g = m->T(p + S(".pre_transformer.norm_layers_2.%d.gamma", l));
-        e.n2b = m->T(p + S(".pre_transformer.norm_layers_2.%d.beta", l));
-        std::string ff = p + S(".pre_transformer.ffn_layers.%d", l);
-        WETTS_TRY(pack(m, ff + ".conv_1.weight", ff + ".conv_1.bias", Hh, Hh, 3, 1, 1, 0, 0, s, &e.f1));
-        WETTS_TRY(pack(m, ff + ".conv_2.weight", ff + ".conv_2.bias", Hh, Hh, 3, 1, 1, 0, 0, s, &e.f2));
-      }
+      for (int l = 0; l < 2; ++l) WETTS_TRY(load_enc_layer(m, q + ".pre_transformer", l, s, &tr[l]));
     }
   }
 
   if (c->vocoder_type == 1) return build_vocos(m, s);
 
-  const int C0 = c->upsample_initial_channel;
-  WETTS_TRY(pack(m, "dec.conv_pre.weight", "dec.conv_pre.bias", C0, I, 7, 1, 3, 0, 0, s,
-                 &m->conv_pre));
   m->ups.resize(c->n_upsamples);
   m->rbs.resize(c->n_upsamples * c->n_resblock_kernels);
-  int ch = C0;
+  for (RB& rb : m->rbs) {
+    rb.c1.resize(c->n_resblock_dilations);
+    if (c->resblock == 1) rb.c2.resize(c->n_resblock_dilations);
+  }
   m->hop = 1;
-  for (int i = 0; i < c->n_upsamples; ++i) {
-    const int u = c->upsample_rates[i], uk = c->upsample_kernel_sizes[i];
-    WETTS_TRY(pack(m, S("dec.ups.%d.weight", i), S("dec.ups.%d.bias", i), ch / 2, ch, uk, 1,
-                   (uk - u) / 2, 1, u, s, &m->ups[i]));
-    ch /= 2;
-    m->hop *= u;
-    for (int j = 0; j < c->n_resblock_kernels; ++j) {
-      int n = i * c->n_resblock_kernels + j;
-      int k = c->resblock_kernel_sizes[j];
-      RB& rb = m->rbs[n];
-      rb.c1.resize(c->n_resblock_dilations);
-      if (c->resblock == 1) rb.c2.resize(c->n_resblock_dilations);
-      for (int d = 0; d < c->n_resblock_dilations; ++d) {
-        int dil = c->resblock_dilation_sizes[j][d];
-        int pad = (k * dil - dil) / 2;  // get_padding, commons.py:13-14
-        if (c->resblock == 1) {
-          WETTS_TRY(pack(m, S("dec.resblocks.%d.convs1.%d.weight", n, d),
-                         S("dec.resblocks.%d.convs1.%d.bias", n, d), ch, ch, k, dil, pad, 0, 0, s,
-                         &rb.c1[d]));
-          WETTS_TRY(pack(m, S("dec.resblocks.%d.convs2.%d.weight", n, d),
-                         S("dec.resblocks.%d.convs2.%d.bias", n, d), ch, ch, k, 1, (k - 1) / 2, 0,
-                         0, s, &rb.c2[d]));
-        } else {
-          WETTS_TRY(pack(m, S("dec.resblocks.%d.convs.%d.weight", n, d),
-                         S("dec.resblocks.%d.convs.%d.bias", n, d), ch, ch, k, dil, pad, 0, 0, s,
-                         &rb.c1[d]));
-        }
-      }
-    }
+  for (const GenConv& g : hifigan_convs(c)) {
+    PackedConv* pc = g.kind == GenConv::PRE  ? &m->conv_pre
+                     : g.kind == GenConv::UP ? &m->ups[g.i]
+                     : g.kind == GenConv::C1 ? &m->rbs[g.n].c1[g.d]
+                     : g.kind == GenConv::C2 ? &m->rbs[g.n].c2[g.d]
+                                             : nullptr;  // conv_post, cond: read in their natural layout, below
+    if (pc) WETTS_TRY(load_conv(m, g.prefix, s, pc));
+    if (g.kind == GenConv::UP) m->hop *= g.up;
   }
   m->conv_post_w = m->T("dec.conv_post.weight");
   m->dec_cond_w = m->T("dec.cond.weight");
   m->dec_cond_b = m->T("dec.cond.bias");
   return WETTS_OK;
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // workspace sizing
@@ -1062,13 +1016,11 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
       }
     }
     if (r == WETTS_OK && !m->wn_gate) {  // A/B: the in_layers back in the reference's row order, gate_kernel behind them
-      const int H = cfg->hidden_channels, fk = cfg->flow_kernel_size;
       for (int f = 0; f < cfg->flow_n_flows && r == WETTS_OK; ++f)
         for (int i = 0; i < cfg->flow_wn_layers && r == WETTS_OK; ++i) {
-          const std::string p = S("flow.flows.%d.enc.in_layers.%d", flow_key_stride(cfg) * f, i);
           free_packed(&m->flows[f].in_layers[i]);
-          r = pack_conv_weight(m->T(p + ".weight"), m->T(p + ".bias"), 2 * H, H, fk, 1, (fk - 1) / 2, 0, 0, s,
-                               &m->flows[f].in_layers[i]);
+          r = pack(m->layout, m->blob, S("flow.flows.%d.enc.in_layers.%d", flow_key_stride(cfg) * f, i), s,
+                   &m->flows[f].in_layers[i]);
         }
     }
     if (m->mrf_streams < 1) m->mrf_streams = 1;
@@ -1503,22 +1455,12 @@ static void free_flow_bf16(const wetts_model* m) {
 
 static int32_t pack_flow_bf16_layers(const wetts_model* m, int f16, hipStream_t s) {
   const wetts_config_t* c = &m->cfg;
-  const int H = c->hidden_channels, NL = c->flow_wn_layers, fk = c->flow_kernel_size;
+  const int H = c->hidden_channels, NL = c->flow_wn_layers;
   m->b_wn_in.assign(c->flow_n_flows, std::vector<PackedConvB>(NL));
   m->b_wn_rs.assign(c->flow_n_flows, std::vector<PackedConvB>(NL));
-  for (int f = 0; f < c->flow_n_flows; ++f) {
-    const std::string p = S("flow.flows.%d", flow_key_stride(c) * f);
-    for (int i = 0; i < NL; ++i) {
-      WETTS_TRY(pack_conv_weight_bf16(m->T(p + S(".enc.in_layers.%d.weight", i)),
-                                      m->T(p + S(".enc.in_layers.%d.bias", i)), 2 * H, H, fk, 1,
-                                      (fk - 1) / 2, 0, 0, f16, s, &m->b_wn_in[f][i],
-                                      wn16_fused(H) ? H : 0));
-      const int rs = (i < NL - 1) ? 2 * H : H;
-      WETTS_TRY(pack_conv_weight_bf16(m->T(p + S(".enc.res_skip_layers.%d.weight", i)),
-                                      m->T(p + S(".enc.res_skip_layers.%d.bias", i)), rs, H, 1, 1, 0,
-                                      0, 0, f16, s, &m->b_wn_rs[f][i]));
-    }
-  }
+  for (int f = 0; f < c->flow_n_flows; ++f)
+    WETTS_TRY(pack_wn(m->layout, m->blob, S("flow.flows.%d.enc", flow_key_stride(c) * f), NL, wn16_fused(H) ? H : 0, s,
+                      nullptr, nullptr, &m->b_wn_in[f], &m->b_wn_rs[f], f16));
   return WETTS_OK;
 }
 
@@ -1806,43 +1748,31 @@ int32_t wetts_flow_reverse(const wetts_model_t* m, const float* z_p_in, const fl
 namespace wetts {
 static int32_t build_posterior(wetts_model* m, int spec, const float* blob_dev, int64_t numel, hipStream_t s) {
   const wetts_config_t* c = &m->cfg;
-  const int H = c->hidden_channels, I = c->inter_channels;
   build_posterior_layout(c, spec, m->post_layout);
   WETTS_REQUIRE(numel == m->post_layout.total, "posterior blob has %lld floats, layout needs %lld", (long long)numel,
                 (long long)m->post_layout.total);
   WETTS_HIP_CHECK(hipMalloc((void**)&m->post_blob, (size_t)numel * sizeof(float)));
   WETTS_HIP_CHECK(hipMemcpyAsync(m->post_blob, blob_dev, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, s));
   m->spec_channels = spec;
-  auto PT = [&](const std::string& name) -> const float* {
-    auto it = m->post_layout.index.find(name);
-    return it == m->post_layout.index.end() ? nullptr : m->post_blob + m->post_layout.specs[it->second].offset;
-  };
+  const Layout& PL = m->post_layout;
   // pre: K = spec_channels (513: odd) -- the packing zero-fills the K tail of the last 16-channel chunk, and the conv
   // kernels predicate the input channel, so the caller's spectrogram is read in place
-  WETTS_TRY(pack_conv_weight(PT("enc_q.pre.weight"), PT("enc_q.pre.bias"), H, spec, 1, 1, 0, 0, 0, s, &m->pe_pre));
+  WETTS_TRY(pack(PL, m->post_blob, "enc_q.pre", s, &m->pe_pre));
   m->pe_in.resize(kPostLayers);
   m->pe_rs.resize(kPostLayers);
-  for (int i = 0; i < kPostLayers; ++i) {
-    // dilation_rate 1 (models.py:125-133): dilation 1, padding 2; rows interleaved for the gate epilogue like the flow's
-    WETTS_TRY(pack_conv_weight(PT(S("enc_q.enc.in_layers.%d.weight", i)), PT(S("enc_q.enc.in_layers.%d.bias", i)), 2 * H,
-                               H, kPostKernel, 1, (kPostKernel - 1) / 2, 0, 0, s, &m->pe_in[i], 0, m->wn_gate ? H : 0));
-    const int rs = (i < kPostLayers - 1) ? 2 * H : H;
-    WETTS_TRY(pack_conv_weight(PT(S("enc_q.enc.res_skip_layers.%d.weight", i)),
-                               PT(S("enc_q.enc.res_skip_layers.%d.bias", i)), rs, H, 1, 1, 0, 0, 0, s, &m->pe_rs[i]));
-  }
-  m->pe_cond_w = PT("enc_q.enc.cond_layer.weight");
-  m->pe_cond_b = PT("enc_q.enc.cond_layer.bias");
-  WETTS_TRY(pack_conv_weight(PT("enc_q.proj.weight"), PT("enc_q.proj.bias"), 2 * I, H, 1, 1, 0, 0, 0, s, &m->pe_proj));
+  // rows interleaved for the gate epilogue like the flow's (unless the wn_gate A/B switched that off)
+  WETTS_TRY(pack_wn(PL, m->post_blob, "enc_q.enc", kPostLayers, m->wn_gate ? c->hidden_channels : 0, s, &m->pe_in,
+                    &m->pe_rs));
+  m->pe_cond_w = tensor(PL, m->post_blob, "enc_q.enc.cond_layer.weight");
+  m->pe_cond_b = tensor(PL, m->post_blob, "enc_q.enc.cond_layer.bias");
+  WETTS_TRY(pack(PL, m->post_blob, "enc_q.proj", s, &m->pe_proj));
   // forward flow: x0 = x[:, :I/2] in natural order.  The pre_conv type's `pre` is packed that way already; every other
   // type (plain, pre_conv2, the mono types' coupling layer) gets a second copy without the reversed input channels the
   // reverse direction reads (build_model)
   m->fwd_pre.resize(c->flow_n_flows);
   if (c->transformer_flows != 1)
-    for (int f = 0; f < c->flow_n_flows; ++f) {
-      const std::string p = S("flow.flows.%d", flow_key_stride(c) * f);
-      WETTS_TRY(pack_conv_weight(m->T(p + ".pre.weight"), m->T(p + ".pre.bias"), H, I / 2, 1, 1, 0, 0, 0, s,
-                                 &m->fwd_pre[f]));
-    }
+    for (int f = 0; f < c->flow_n_flows; ++f)
+      WETTS_TRY(pack(m->layout, m->blob, S("flow.flows.%d.pre", flow_key_stride(c) * f), s, &m->fwd_pre[f]));
   return WETTS_OK;
 }
 }  // namespace wetts
@@ -2586,33 +2516,15 @@ static int32_t pack_decoder_bf16_layers(const wetts_model* m, int f16, hipStream
   m->b_ups.resize(c->n_upsamples);
   m->b_c1.assign(c->n_upsamples * nk, std::vector<PackedConvB>(nd));
   m->b_c2.assign(c->n_upsamples * nk, std::vector<PackedConvB>(c->resblock == 1 ? nd : 0));
-  int ch = c->upsample_initial_channel;
-  WETTS_TRY(pack_conv_weight_bf16(m->T("dec.conv_pre.weight"), m->T("dec.conv_pre.bias"), ch, c->inter_channels, 7, 1, 3,
-                                  0, 0, f16, s, &m->b_pre));
-  for (int i = 0; i < c->n_upsamples; ++i) {
-    const int u = c->upsample_rates[i], uk = c->upsample_kernel_sizes[i];
-    WETTS_TRY(pack_conv_weight_bf16(m->T(S("dec.ups.%d.weight", i)), m->T(S("dec.ups.%d.bias", i)),
-                                    ch / 2, ch, uk, 1, (uk - u) / 2, 1, u, f16, s, &m->b_ups[i]));
-    ch /= 2;
-    for (int j = 0; j < nk; ++j) {
-      const int n = i * nk + j, k = c->resblock_kernel_sizes[j];
-      for (int d = 0; d < nd; ++d) {
-        const int dil = c->resblock_dilation_sizes[j][d];
-        if (c->resblock == 1) {
-          WETTS_TRY(pack_conv_weight_bf16(m->T(S("dec.resblocks.%d.convs1.%d.weight", n, d)),
-                                          m->T(S("dec.resblocks.%d.convs1.%d.bias", n, d)), ch, ch,
-                                          k, dil, (k * dil - dil) / 2, 0, 0, f16, s, &m->b_c1[n][d]));
-          WETTS_TRY(pack_conv_weight_bf16(m->T(S("dec.resblocks.%d.convs2.%d.weight", n, d)),
-                                          m->T(S("dec.resblocks.%d.convs2.%d.bias", n, d)), ch, ch,
-                                          k, 1, (k - 1) / 2, 0, 0, f16, s, &m->b_c2[n][d]));
-        } else {
-          WETTS_TRY(pack_conv_weight_bf16(m->T(S("dec.resblocks.%d.convs.%d.weight", n, d)),
-                                          m->T(S("dec.resblocks.%d.convs.%d.bias", n, d)), ch, ch,
-                                          k, dil, (k * dil - dil) / 2, 0, 0, f16, s, &m->b_c1[n][d]));
-        }
-      }
-    }
+  for (const GenConv& g : hifigan_convs(c)) {
+    PackedConvB* pc = g.kind == GenConv::PRE  ? &m->b_pre
+                      : g.kind == GenConv::UP ? &m->b_ups[g.i]
+                      : g.kind == GenConv::C1 ? &m->b_c1[g.n][g.d]
+                      : g.kind == GenConv::C2 ? &m->b_c2[g.n][g.d]
+                                              : nullptr;  // conv_post: below; cond: an f32 bias (k_cond_linear)
+    if (pc) WETTS_TRY(pack16(m->layout, m->blob, g.prefix, f16, s, pc));
   }
+  const int ch = c->upsample_initial_channel >> c->n_upsamples;
   if (ch == 32) {  // conv_post on the matrix cores (k_conv_post_mfma16): rows 1..31 of the weight are zero
     const size_t n = (size_t)32 * ch * 7;
     if (!m->b_post_wpad) WETTS_HIP_CHECK(hipMalloc((void**)&m->b_post_wpad, n * sizeof(float)));
@@ -2833,38 +2745,18 @@ static void free_decoder_u8(const wetts_model* m) {
 
 static int32_t pack_decoder_u8_layers(const wetts_model* m, hipStream_t s) {
   const wetts_config_t* c = &m->cfg;
-  const int I = c->inter_channels, C0 = c->upsample_initial_channel;
   const int nk = c->n_resblock_kernels, nd = c->n_resblock_dilations;
-  WETTS_TRY(pack_qconv_weight(m->T("dec.conv_pre.weight"), m->T("dec.conv_pre.bias"), C0, I, 7, 1, 3, s,
-                              &m->q_pre));
-  if (has_g(c))
-    WETTS_TRY(pack_qconv_weight(m->T("dec.cond.weight"), m->T("dec.cond.bias"), C0, c->gin_channels, 1,
-                                1, 0, s, &m->q_cond));
   m->q_c1.assign(c->n_upsamples * nk, std::vector<PackedQConv>(nd));
   m->q_c2.assign(c->n_upsamples * nk, std::vector<PackedQConv>(c->resblock == 1 ? nd : 0));
-  int ch = C0;
-  for (int i = 0; i < c->n_upsamples; ++i) {
-    ch /= 2;
-    for (int j = 0; j < nk; ++j) {
-      const int n = i * nk + j, k = c->resblock_kernel_sizes[j];
-      for (int d = 0; d < nd; ++d) {
-        const int dil = c->resblock_dilation_sizes[j][d];
-        if (c->resblock == 1) {
-          WETTS_TRY(pack_qconv_weight(m->T(S("dec.resblocks.%d.convs1.%d.weight", n, d)),
-                                      m->T(S("dec.resblocks.%d.convs1.%d.bias", n, d)), ch, ch, k, dil,
-                                      (k * dil - dil) / 2, s, &m->q_c1[n][d]));
-          WETTS_TRY(pack_qconv_weight(m->T(S("dec.resblocks.%d.convs2.%d.weight", n, d)),
-                                      m->T(S("dec.resblocks.%d.convs2.%d.bias", n, d)), ch, ch, k, 1,
-                                      (k - 1) / 2, s, &m->q_c2[n][d]));
-        } else {
-          WETTS_TRY(pack_qconv_weight(m->T(S("dec.resblocks.%d.convs.%d.weight", n, d)),
-                                      m->T(S("dec.resblocks.%d.convs.%d.bias", n, d)), ch, ch, k, dil,
-                                      (k * dil - dil) / 2, s, &m->q_c1[n][d]));
-        }
-      }
-    }
+  for (const GenConv& g : hifigan_convs(c)) {
+    PackedQConv* pc = g.kind == GenConv::PRE    ? &m->q_pre
+                      : g.kind == GenConv::C1   ? &m->q_c1[g.n][g.d]
+                      : g.kind == GenConv::C2   ? &m->q_c2[g.n][g.d]
+                      : g.kind == GenConv::POST ? &m->q_post
+                      : g.kind == GenConv::COND ? &m->q_cond
+                                                : nullptr;  // ConvTranspose1d stays f32 (export_onnx.py:149-157)
+    if (pc) WETTS_TRY(packq(m->layout, m->blob, g.prefix, s, pc));
   }
-  WETTS_TRY(pack_qconv_weight(m->T("dec.conv_post.weight"), nullptr, 1, ch, 7, 1, 3, s, &m->q_post));
   return WETTS_OK;
 }
 
