@@ -508,7 +508,8 @@ def onnx_stft_inverse(mag, phase, n_fft, hop, win_length):
     """OnnxSTFT.inverse (utils/stft.py:325-340): conv_transpose1d of [mag cos; mag sin] with the inverse basis at
     stride hop, n_fft/2 samples cut from each end.  No window-envelope division."""
     x = torch.cat([mag * torch.cos(phase), mag * torch.sin(phase)], dim=1)
-    o = F.conv_transpose1d(x, onnx_stft_inverse_basis(n_fft, hop, win_length), stride=hop, padding=0)
+    # (the buffer is float32 in the reference; a float64 run widens those values)
+    o = F.conv_transpose1d(x, onnx_stft_inverse_basis(n_fft, hop, win_length).to(x.dtype), stride=hop, padding=0)
     o = o[:, :, int(n_fft / 2):]
     return o[:, :, :-int(n_fft / 2)]
 

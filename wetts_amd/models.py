@@ -744,6 +744,10 @@ class SynthesizerTrn:
         B = z.shape[0]
         if B == 0 or L == 0:  # (z * y_mask)[:, :, :0] -> empty audio, nothing to launch
             return torch.empty(B, 1, 0, dtype=torch.float32, device=self.device)
+        if z.shape[2] > 1 and z.stride(2) != 1:
+            # the C entry takes a batch and a channel stride and reads time at stride 1: a time-major view (an ORT
+            # [B, L, inter] tensor transposed) would be read as garbage without an error
+            z = z.contiguous()
         if self.overlap:  # the next call's encoder stages may be using self._ws on the side stream by now
             nws = lib.wetts_workspace_bytes(self._handle, B, 0, L)
             if nws < 0:
