@@ -186,8 +186,9 @@ def test_ragged_and_degenerate_batches():
                                    "tiny_mono_post_b2", "tiny_mono_inter_b3"])
 def test_random_small_shapes_match_the_oracle(cname):
     """Odd batch sizes and text lengths (B = 1..5, Tx = 1..23, ragged, length-1 utterances) against the
-    oracle on the same padded batch: these are the shapes the small-launch conv schedule, the scalar
-    attention path and every partial tile see; alignment must be EQUAL, audio within 1e-4 RMS."""
+    oracle on the same padded batch: these are the shapes the small-launch conv schedule, the one-launch
+    attention kernel (attn_small_kernel; the scalar attention kernels are only its fallback now, reached by
+    tests/test_gpu_encoder_oracle.py) and every partial tile see; alignment must be EQUAL, audio within 1e-4 RMS."""
     from oracle import vits_oracle as vo
     net, case, cfg, sd, W = _model(cname)
     cd = util.cfg_dict(cfg)

@@ -317,10 +317,10 @@ def test_vits2_v1_hifigan_with_transformer_flows_matches_oracle():
 
 
 def test_text_encoder_mfma_attention_matches_oracle_ragged():
-    """Tx >= 64 routes the relative-position attention through the matrix-core kernels
-    (attention.hip: band term from a [2w+1] x T table in the score epilogue, relative-value pass
-    after P.V); the golden cases (Tx <= 12) cover the scalar path.  Ragged lengths exercise the
-    -1e4 masking; Tx = 100 is not a multiple of the 32-wide tiles."""
+    """Tx = 100 runs the relative-position attention in the one-launch attn_small_kernel (attention.hip: every windowed
+    attention up to 128 positions, four 32-query strips here, 16-byte staging since 100 is a multiple of 4), as the
+    golden cases (Tx <= 12) do; the matrix-core kernels take over from Tx = 129 and are held to the float64 oracle by
+    tests/test_gpu_encoder_oracle.py.  Ragged lengths exercise the -1e4 masking."""
     from oracle import vits_oracle as vo
     from wetts_amd import checkpoint
     net, sd = _net("v1", 120, 1, seed=5)

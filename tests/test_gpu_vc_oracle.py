@@ -4,9 +4,14 @@ shapes the fixed goldens never reach: every flow type at tiny and ragged batches
 and 1 mod 16, full-size batches on the big conv tiles, inputs with garbage beyond y_lengths, the 16-bit forward flow
 against its numerics spec, and the device noise draw against Philox.
 
+The transformer-flow models run a second list at tile-edge frame counts (TILE_SHAPES): the oracle otherwise sees their
+attention at no Ty above 23.
+
 Every comparison is over whole tensors of the same padded batch, padded frames included, with two gates per stage:
 rel RMS <= 1e-5 and max |d| / rms(ref) <= 1e-4 (a local-error gate: one wrong tile or last frame does not hide in a
 whole-tensor RMS).  Audio: abs RMS <= 1e-4, as in the infer() sweep.  Each test prints its worst figures per stage."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -25,14 +30,40 @@ FLOW_MODELS = ["tiny", "vits2_v1", "tiny_preconv2_spk", "tiny_mono_post", "tiny_
 SHAPES = [(1, 1, [1]), (1, 2, [2]), (1, 3, [2]), (1, 4, [4]), (1, 5, [5]), (2, 7, [7, 1]), (3, 23, [1, 23, 12]),
           (5, 9, [3, 8, 1, 5, 6]), (4, 16, [16, 1, 9, 14]), (2, 17, [1, 11])]
 
+# The transformer flows at tile-edge frame counts.  Ty_in: the 32-query strips and 32-key tiles of attn_flash_kernel
+# (window-less, dk = 48: its four waves walk the keys in strides of 128, so 129 .. 256 frames give a wave a second
+# tile, 545 frames five to wave 0 with one key in the last) and of the windowed kernels of the pre_conv2 flows
+# (dk = 96: attn_small_kernel up to 128 frames, the matrix-core path with three 32-row d-blocks beyond).  Ragged: one
+# full row, one of length 1, one 1 past a multiple of 32; B cycles over 1, 2, 3.
+# tests/test_cpu_encoder_gate.py asserts what the list reaches of each kernel form.
+TF_MODELS = ["vits2_v1", "tiny_preconv2_spk", "tiny_mono_post", "tiny_mono_inter", "tiny_vits2_vocos"]
+TILE_LENGTHS = (31, 32, 33, 63, 64, 65, 127, 128, 129, 160, 161, 257, 545)
 
-def _model(mname, n_vocab=40, n_spk=3, spec=SPEC, wseed=81, pseed=82):
-    """(device net, cfg dict, float64 folded weights incl. enc_q) of a synthetic checkpoint."""
+
+def _tile_rows(B, Ty):
+    rows = [Ty, 1, 32 * ((Ty - 2) // 32) + 1 if Ty >= 34 else max(1, Ty - 2)][:B]
+    return rows[Ty % B:] + rows[:Ty % B]
+
+
+TILE_SHAPES = [((1, 2, 3)[i % 3], Ty, _tile_rows((1, 2, 3)[i % 3], Ty)) for i, Ty in enumerate(TILE_LENGTHS)]
+# (model, WETTS_TUNE at create): pre_conv2 a second time on the kernels behind the one-launch attention -- the scalar
+# ones below 64 frames, the matrix-core path from 64
+TILE_SWEEP = [(m, None) for m in TF_MODELS] + [("tiny_preconv2_spk", "attn_small_max_t=0")]
+
+
+def _model(mname, n_vocab=40, n_spk=3, spec=SPEC, wseed=81, pseed=82, tune=None):
+    """(device net, cfg dict, float64 folded weights incl. enc_q) of a synthetic checkpoint; `tune`: WETTS_TUNE at
+    create (a per-model setting)."""
     cfg = config.make_config(dict(config.MODEL_CONFIGS[mname]), n_vocab, n_spk)
     sd = synth.make_state_dict(cfg, wseed)
     psd = synth.make_posterior_state_dict(cfg, spec, pseed)
     net = SynthesizerTrn(n_vocab, spec, 32, n_speakers=n_spk, **config.MODEL_CONFIGS[mname])
-    net.load_state_dict(dict(sd, **psd)).to("cuda")
+    if tune is not None:
+        os.environ["WETTS_TUNE"] = tune
+    try:
+        net.load_state_dict(dict(sd, **psd)).to("cuda")
+    finally:
+        os.environ.pop("WETTS_TUNE", None)
     return net, util.cfg_dict(cfg), util.vc_weights(cfg, sd, psd, torch.float64)
 
 
@@ -123,6 +154,35 @@ def test_vc_shape_sweep_matches_float64_oracle(mname):
         y, yl, ss, st, eps = _batch(B, SPEC, Ty, lengths, seed=100 + i)
         _check((mname, B, Ty), _gpu(net, y, yl, ss, st, eps), _oracle(W, cd, y, yl, ss, st, eps), STAGES, worst)
     _report(f"{mname} shape sweep", worst)
+
+
+# ---- a2. the transformer flows at tile-edge frame counts ---------------------------------------------------------------
+_TILE_REFS = {}
+
+
+def _tile_refs(mname):
+    """[(B, Ty, batch, float64 oracle stages)] over TILE_SHAPES: computed once per model, shared by its forms."""
+    if mname not in _TILE_REFS:
+        cfg = config.make_config(dict(config.MODEL_CONFIGS[mname]), 40, 3)
+        W = util.vc_weights(cfg, synth.make_state_dict(cfg, 81), synth.make_posterior_state_dict(cfg, SPEC, 82),
+                            torch.float64)
+        cd, out = util.cfg_dict(cfg), []
+        for i, (B, Ty, lengths) in enumerate(TILE_SHAPES):
+            batch = _batch(B, SPEC, Ty, lengths, seed=300 + i)
+            out.append((B, Ty, batch, _oracle(W, cd, *batch, decode=False)))
+        _TILE_REFS[mname] = out
+    return _TILE_REFS[mname]
+
+
+@pytest.mark.parametrize("mname,tune", TILE_SWEEP)
+def test_vc_transformer_flows_at_tile_edges_match_float64_oracle(mname, tune):
+    """Posterior encoder, forward flow and flow^-1 (no decode) of every transformer-flow model over TILE_SHAPES, at this
+    file's gates."""
+    net, cd, W = _model(mname, tune=tune)
+    worst = {}
+    for B, Ty, batch, ref in _tile_refs(mname):
+        _check((mname, tune, B, Ty), _gpu(net, *batch), ref, STAGES, worst)
+    _report(f"{mname} {tune or 'default'} tile-edge sweep", worst)
 
 
 # ---- b. spec_channels: the posterior pre conv's K tail ------------------------------------------------------------

@@ -655,18 +655,16 @@ __global__ __launch_bounds__(1024) void attn_small_kernel(
   }
 }
 
-// longest sequence the one-launch kernel covers (longer ones take the multi-kernel paths)
-static int attn_small_max_t() { return 128; }
-
 int32_t k_rel_attention(const float* q, const float* k, const float* v, int64_t qkv_batch_stride,
                         const float* mask, const float* emb_rel_k, const float* emb_rel_v,
-                        int window, int B, int n_heads, int dk, int T, float* scores, float* out,
-                        hipStream_t s) {
+                        int window, int B, int n_heads, int dk, int T, int small_max_t, float* scores,
+                        float* out, hipStream_t s) {
   const int64_t qbs = qkv_batch_stride;
   if (B * T == 0) return WETTS_OK;
   WETTS_REQUIRE(T <= 65535, "attention length %d too large", T);
   const float qdiv = (float)sqrt((double)dk);
-  if (window >= 0 && T <= min(attn_small_max_t(), 128)) {  // 32 groups x 4 keys
+  // small_max_t: the longest sequence the one-launch kernel takes (longer ones take the multi-kernel paths)
+  if (window >= 0 && T <= min(small_max_t, 128)) {  // 32 groups x 4 keys
     const size_t lds = attn_small_layout(T, dk, window).lds;
     static signed char opt_in[64] = {};
     // (a device that refuses the large-LDS opt-in takes the general path below)

@@ -160,10 +160,12 @@ int32_t k_add(const float* a, const float* b, int64_t n, float* out, hipStream_t
 //   batch stride in floats (H*dk*T when they are separate contiguous tensors)
 //   window < 0 (no relative terms; the VITS2 flow encoders) and dk <= 48: one flash-style kernel, the T*T
 //   part of the workspace stays untouched (WETTS_ATTN_FLASH=0 selects the three-kernel path)
+//   small_max_t: windowed attention of at most this many positions (and at most 128) is one launch of
+//   attn_small_kernel; 0 sends every length to the multi-kernel paths (the model's attn_small_max_t, default 128)
 int32_t k_rel_attention(const float* q, const float* k, const float* v, int64_t qkv_batch_stride,
                         const float* mask, const float* emb_rel_k, const float* emb_rel_v,
-                        int window, int B, int n_heads, int dk, int T, float* scores, float* out,
-                        hipStream_t s);
+                        int window, int B, int n_heads, int dk, int T, int small_max_t, float* scores,
+                        float* out, hipStream_t s);
 
 // scores-workspace floats k_rel_attention needs in FRONT of its vT / rel-table regions: B*H*T*T on
 // the three-kernel path, 0 on the flash path (shared by the workspace sizing in model.hip)

@@ -515,7 +515,7 @@ __global__ void spline_inverse_kernel(float* __restrict__ z, int ch0, int ch1,
     const float in_h = chh[bin + 1] - chh[bin];
     const float in_delta = in_h / in_bw;
     // derivatives: pad both ends with log(exp(1-min_d)-1)
-    const float cst = (float)0.5408847652626036;  // np.log(np.exp(1 - 1e-3) - 1)
+    const float cst = (float)0.5397424172369522;  // np.log(np.exp(1 - 1e-3) - 1): the end derivatives come out as 1
     float ud0 = (bin == 0) ? cst : hp[(int64_t)(2 * nb + bin - 1) * T];
     float ud1 = (bin == nb - 1) ? cst : hp[(int64_t)(2 * nb + bin) * T];
     const float d0 = min_d + softplus_f(ud0);

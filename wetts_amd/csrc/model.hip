@@ -470,6 +470,10 @@ struct wetts_model {
   // wastes at most this share of the tile (resblock2_stage16.hip; bit-identical to chain by chain); 0 = never
   int stage2_pct = 30;
   int dds_fused = 1;
+  // WETTS_TUNE attn_small_max_t: longest windowed attention the one-launch attn_small_kernel takes (attention.hip; at
+  // most 128, the kernel's 32 groups x 4 keys).  0: never -- the tests' way to the scalar kernels (T < 64) and to the
+  // matrix-core path at 64 <= T <= 128, which the default dispatch reaches only when the large-LDS opt-in is refused
+  int attn_small_max_t = 128;
   int wn_gate = 1;      // WETTS_TUNE wn_gate: the f32 flow's gate in the in_layer conv's epilogue (0: gate_kernel on the 2H-row tensor)
   int wn_fuse = 1;      // WETTS_TUNE wn_fuse: the f32 flow's residual / skip update in the res_skip conv's epilogue (1: small launches, 2: always, 0: wn_update_kernel)
   int small_fork = 1;   // WETTS_TUNE small_fork: the chains of a small (streaming-window) stage on their own streams
@@ -991,7 +995,7 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
         {"stage2_pct", &m->stage2_pct}, {"dds_fused", &m->dds_fused}, {"wn_fuse", &m->wn_fuse}, {"wn_gate", &m->wn_gate},
         {"fuse2_waste_pct", &m->fuse2_waste_pct}, {"fuse_min_blocks", &m->fuse_min_blocks},
         {"chain_whole_pct", &m->chain_whole_waste_pct}, {"chain_whole_maxc", &m->chain_whole_maxc},
-        {"small_max_tiles", &m->small_max_tiles},
+        {"small_max_tiles", &m->small_max_tiles}, {"attn_small_max_t", &m->attn_small_max_t},
     };
     if (const char* env = getenv("WETTS_TUNE")) {
       std::string all(env);
@@ -1138,7 +1142,8 @@ namespace wetts {
 static int32_t run_enc_layers(const std::vector<EncLayer>& layers, float* xa, const float* x_mask,
                               int B, int H, int F, int nh, int window, int T, float* q, float* k,
                               float* v, float* att, float* y, float* hid, float* sc, float* xb,
-                              hipStream_t s, const float* spk_cond = nullptr, int cond_idx = -1) {
+                              hipStream_t s, int attn_small_max_t, const float* spk_cond = nullptr,
+                              int cond_idx = -1) {
   const int dk = H / nh, n = (int)layers.size();
   for (int l = 0; l < n; ++l) {
     const EncLayer& e = layers[l];
@@ -1149,7 +1154,7 @@ static int32_t run_enc_layers(const std::vector<EncLayer>& layers, float* xa, co
     WETTS_TRY(launch_conv(e.qkv, conv_io(xa, H, T, q, 3 * H, B), s));
     const float* qp = q;
     WETTS_TRY(k_rel_attention(qp, qp + (int64_t)H * T, qp + (int64_t)2 * H * T, (int64_t)3 * H * T,
-                              x_mask, e.rel_k, e.rel_v, window, B, nh, dk, T, sc, att, s));
+                              x_mask, e.rel_k, e.rel_v, window, B, nh, dk, T, attn_small_max_t, sc, att, s));
     (void)k; (void)v;
     WETTS_TRY(launch_conv(e.o, conv_io(att, H, T, y, H, B), s));
     // x = norm_layers_1(x + y), written MASKED: columns with mask 0 are zero from here on.  That is what the FFN wants
@@ -1212,7 +1217,7 @@ int32_t wetts_text_encoder(const wetts_model_t* m, const int64_t* x, const int64
   float* xa = x_enc;  // current activations live in xa
   WETTS_TRY(k_embed_mask(x, x_lengths, m->emb, c->n_vocab, B, H, Tx, xa, x_mask, m->status_word, s));
   WETTS_TRY(run_enc_layers(m->enc, xa, x_mask, B, H, F, nh, c->window_size, Tx, q, k, v, att, y,
-                           hid, sc, xb, s, spk_on ? spk : nullptr, 2));
+                           hid, sc, xb, s, m->attn_small_max_t, spk_on ? spk : nullptr, 2));
   if (c->n_layers == 0) {
     // Encoder with no layers still masks its input; embed_mask already did.
   }
@@ -1686,7 +1691,7 @@ int32_t wetts_flow_reverse(const wetts_model_t* m, const float* z_p_in, const fl
       const float sc = c->transformer_flows == 4 ? 0.5f : 1.f;
       float* mdst = (cur == xa) ? xb : xa;
       WETTS_TRY(k_mono_split(cur, y_mask, B, I, Ty, sc, tx0, txm, s));  // x0 * sc, and x0 * sc * mask
-      WETTS_TRY(run_enc_layers(fw.mono_tr, txm, y_mask, B, Hh, Hh, 2, -1, Ty, tq, tk, tv, tatt, ty, thid, tsc, txb, s));
+      WETTS_TRY(run_enc_layers(fw.mono_tr, txm, y_mask, B, Hh, Hh, 2, -1, Ty, tq, tk, tv, tatt, ty, thid, tsc, txb, s, m->attn_small_max_t));
       if (c->transformer_flows == 3) WETTS_TRY(k_add(txm, tx0, (int64_t)B * Hh * Ty, txm, s));
       ConvParams p = conv_io(txm, Hh, Ty, mm, Hh, B);
       p.out_mask = y_mask;
@@ -1704,7 +1709,7 @@ int32_t wetts_flow_reverse(const wetts_model_t* m, const float* z_p_in, const fl
       const int Hh = I / 2;
       WETTS_TRY(k_flip_half(cur, y_mask, B, I, Ty, tx0, txm, s));  // raw x0, and x0 * mask
       WETTS_TRY(run_enc_layers(fw.pre_tr, txm, y_mask, B, Hh, Hh, 2, -1, Ty, tq, tk, tv, tatt, ty,
-                               thid, tsc, txb, s));
+                               thid, tsc, txb, s, m->attn_small_max_t));
       WETTS_TRY(k_add(txm, tx0, (int64_t)B * Hh * Ty, txm, s));  // vits2 residual connection
       ConvParams p = conv_io(txm, Hh, Ty, h, H, B);               // h = pre(x0_) * mask
       p.out_mask = y_mask;
@@ -1721,7 +1726,7 @@ int32_t wetts_flow_reverse(const wetts_model_t* m, const float* z_p_in, const fl
         WETTS_HIP_CHECK(hipMemcpyAsync(txm, h, (size_t)B * H * Ty * sizeof(float),
                                        hipMemcpyDeviceToDevice, s));
         WETTS_TRY(run_enc_layers(fw.pre_tr, txm, y_mask, B, H, H, 2, 4, Ty, tq, tk, tv, tatt, ty,
-                                 thid, tsc, txb, s));
+                                 thid, tsc, txb, s, m->attn_small_max_t));
         WETTS_TRY(k_add(h, txm, (int64_t)B * H * Ty, h, s));
       }
     }
@@ -1894,7 +1899,7 @@ int32_t wetts_flow_forward(const wetts_model_t* m, const float* z_in, const floa
       // pre_conv (flows.py:145-150): x0_ = pre_transformer(x0 * mask, mask) + x0;  h = pre(x0_) * mask
       WETTS_TRY(k_mono_split(cur, y_mask, B, I, Ty, 1.f, fs.tx0, fs.txm, s));  // x0, x0 * mask
       WETTS_TRY(run_enc_layers(fw.pre_tr, fs.txm, y_mask, B, Hh, Hh, 2, -1, Ty, fs.tq, fs.tk, fs.tv, fs.tatt, fs.ty,
-                               fs.thid, fs.tsc, fs.txb, s));
+                               fs.thid, fs.tsc, fs.txb, s, m->attn_small_max_t));
       WETTS_TRY(k_add(fs.txm, fs.tx0, (int64_t)B * Hh * Ty, fs.txm, s));
       ConvParams p = conv_io(fs.txm, Hh, Ty, fs.h, H, B);
       p.out_mask = y_mask;
@@ -1910,7 +1915,7 @@ int32_t wetts_flow_forward(const wetts_model_t* m, const float* z_in, const floa
         // pre_conv2 (flows.py:64-67): h = h + pre_transformer(h * mask, mask)
         WETTS_HIP_CHECK(hipMemcpyAsync(fs.txm, fs.h, (size_t)B * H * Ty * sizeof(float), hipMemcpyDeviceToDevice, s));
         WETTS_TRY(run_enc_layers(fw.pre_tr, fs.txm, y_mask, B, H, H, 2, 4, Ty, fs.tq, fs.tk, fs.tv, fs.tatt, fs.ty,
-                                 fs.thid, fs.tsc, fs.txb, s));
+                                 fs.thid, fs.tsc, fs.txb, s, m->attn_small_max_t));
         WETTS_TRY(k_add(fs.h, fs.txm, (int64_t)B * H * Ty, fs.h, s));
       }
     }
@@ -1936,7 +1941,7 @@ int32_t wetts_flow_forward(const wetts_model_t* m, const float* z_in, const floa
       //              out = x + [x0, m + x1 * mask]
       WETTS_TRY(k_mono_split(cur, y_mask, B, I, Ty, 1.f, fs.tx0, fs.txm, s));
       WETTS_TRY(run_enc_layers(fw.mono_tr, fs.txm, y_mask, B, Hh, Hh, 2, -1, Ty, fs.tq, fs.tk, fs.tv, fs.tatt, fs.ty,
-                               fs.thid, fs.tsc, fs.txb, s));
+                               fs.thid, fs.tsc, fs.txb, s, m->attn_small_max_t));
       if (tf == 3) WETTS_TRY(k_add(fs.txm, fs.tx0, (int64_t)B * Hh * Ty, fs.txm, s));
       ConvParams p = conv_io(fs.txm, Hh, Ty, fs.mm, Hh, B);
       p.out_mask = y_mask;
