@@ -54,6 +54,8 @@ extern "C" {
 #define WETTS_STATUS_ALIGN_TEXT_LONGER 16 /* some x_lengths[b] > y_lengths[b]: no monotonic alignment exists (the
                                            * reference's search, monotonic_align.py:22-57, returns a meaningless path) */
 #define WETTS_STATUS_DURATION_NEGATIVE 32 /* a negative frame count given to wetts_counts_to_lengths */
+#define WETTS_STATUS_SEGMENT_LONGER 64    /* wetts_slice_ids: an utterance shorter than the decoder segment, or a given
+                                           * slice id outside [0, len - segment] (the reference slices out of range) */
 
 #define WETTS_MAX_STAGES 8
 #define WETTS_MAX_RB_KERNELS 8
@@ -398,6 +400,44 @@ int32_t wetts_path_to_durations(const int32_t* path, const int32_t* t_ys, const 
 int32_t wetts_counts_to_lengths(const int64_t* counts, const float* x_mask, int32_t B, int32_t Tx, float* w_ceil,
                                 float* cum, int64_t* y_lengths, int32_t* status_dev, void* stream);
 
+/* ---- teacher-forced reconstruction (models.py:214-216 and the reconstruction losses of train.py:402-432,486-488) ---- */
+
+/* Where the decoder slice of each utterance starts, commons.py:54-56:
+ *   ids[b] = int64(u[b] * float(len[b] - segment + 1)), the float32 product truncated toward zero,
+ * then clamped into [0, len[b] - segment]: a u of 1.0 (the reference's torch.rand is below 1, a caller's u need not be)
+ * would give len - segment + 1 and slice one frame out of range.  u [B] float (wetts_rand, or the caller's); lengths [B] int64 (NULL = every row holds T),
+ * clamped into [0, T].  With ids_in [B] int64 (then u may be NULL) the caller's ids are taken instead and checked.
+ * A row with len[b] < segment, or a given id outside [0, len[b] - segment], ORs WETTS_STATUS_SEGMENT_LONGER into
+ * status_dev (may be NULL); its id is 0 resp. the nearest valid one, so nothing downstream reads out of bounds. */
+int32_t wetts_slice_ids(const float* u, const int64_t* ids_in, const int64_t* lengths, int32_t B, int32_t T,
+                        int32_t segment, int64_t* ids, int32_t* status_dev, void* stream);
+
+/* commons.slice_segments (commons.py:41-47) with a scale: out[b,c,j] = x[b,c, ids[b]*scale + j] for
+ * j < segment*scale.  x [B,C,T] with batch / channel strides in floats (time stride 1), out [B,C,segment*scale]
+ * contiguous.  scale = 1 slices z or a mel spectrogram at frame ids, scale = hop the waveform at the same ids
+ * (train.py:430-431).  Any C >= 1 and any alignment of base, strides and start; segment*scale <= T.  A start outside
+ * [0, T - segment*scale] is clamped into it (wetts_slice_ids has flagged it). */
+int32_t wetts_slice_segments(const float* x, int64_t x_batch_stride, int64_t x_channel_stride, const int64_t* ids,
+                             int32_t B, int32_t C, int32_t T, int32_t segment, int32_t scale, float* out,
+                             void* stream);
+
+/* losses.kl_loss (losses.py:45-60) without gradients: kl = logs_p - logs_q - 1/2 + 1/2 (z_p - m_p)^2 exp(-2 logs_p) on
+ * [B,I,T] tensors, z_mask [B,T].  partials [2,B]: the masked sums and the frame counts sum_t z_mask per utterance;
+ *   per_utt[b] = partials[0][b] / partials[1][b],   total[0] = sum_b partials[0][b] / sum_b partials[1][b],
+ *   total[1] = weight * total[0]  (the loss as train.py:487 weighs it, `* hps.train.c_kl`)
+ * -- the divisor counts frames, not frames x channels, as the reference's does.  Frames with z_mask == 0 are not read
+ * into the sum.  No floating-point atomics: every sum is formed in a fixed order that depends on an utterance's own
+ * frames only, so results repeat bit for bit and a row alone gives the per_utt it gives inside a padded batch. */
+int32_t wetts_kl_loss(const float* z_p, const float* logs_q, const float* m_p, const float* logs_p,
+                      const float* z_mask, int32_t B, int32_t I, int32_t T, float weight, float* partials,
+                      float* per_utt, float* total, void* stream);
+
+/* F.l1_loss with its default mean (train.py:486) of two contiguous [B,N] tensors: partials [B] = sum_i |a - b| per row,
+ * per_utt[b] = partials[b] / N, total[0] = sum_b partials[b] / (B*N), total[1] = weight * total[0] (`* hps.train.c_mel`).
+ * Summation order as wetts_kl_loss. */
+int32_t wetts_l1_loss(const float* a, const float* b, int32_t B, int64_t N, float weight, float* partials,
+                      float* per_utt, float* total, void* stream);
+
 /* a16 inference.py:100-110 output scaling: per utterance peak-normalise to 0.6 full scale,
  * clip, convert to int16.  lengths_samples [B] int64 = valid samples per row (peak is taken
  * over the valid part only when non-NULL, else over all L samples). */
@@ -408,6 +448,9 @@ int32_t wetts_audio_to_int16(const float* audio, const int64_t* lengths_samples,
  * torch.randn (duration_predictors.py:257) / torch.randn_like (models.py:267).  Element i is a
  * function of (seed, offset, i) only; a draw of n values consumes ceil(n/4) counter steps. */
 int32_t wetts_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
+/* Its uniform counterpart, torch.rand (commons.py:54): floats in [0, 1) from the low 24 bits of each Philox word times
+ * 2^-24 (ATen's mapping for float).  Same (seed, offset) convention, ceil(n/4) counter steps. */
+int32_t wetts_rand(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream);
 
 /* ---- spectrograms (utils/mel_processing.py, inference side).  Need no model. ------------------------------------- */
 

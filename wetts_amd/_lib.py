@@ -94,6 +94,11 @@ SIGNATURES = {
     "wetts_set_status_word": (_I32, [_P, _P, _P]),
     "wetts_set_seed": (_I32, [_P, C.c_uint64]),
     "wetts_randn": (_I32, [_P, _I64, C.c_uint64, C.c_uint64, _P]),
+    "wetts_rand": (_I32, [_P, _I64, C.c_uint64, C.c_uint64, _P]),
+    "wetts_slice_ids": (_I32, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "wetts_slice_segments": (_I32, [_P, _I64, _I64, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "wetts_kl_loss": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    "wetts_l1_loss": (_I32, [_P, _P, _I32, _I64, _F, _P, _P, _P, _P]),
     "wetts_stft_basis_numel": (_I64, [_I32, _I32]),
     "wetts_stft_basis": (_I32, [_I32, _I32, _P, _I64, _P]),
     "wetts_spectrogram": (_I32, [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),
@@ -139,7 +144,7 @@ SIGNATURES = {
 
 # WETTS_STATUS_* bits of include/wetts_hip.h
 STATUS_SPLINE_DOMAIN, STATUS_PHONE_ID_RANGE, STATUS_SPEAKER_ID_RANGE, STATUS_DURATION_NONFINITE = 1, 2, 4, 8
-STATUS_ALIGN_TEXT_LONGER, STATUS_DURATION_NEGATIVE = 16, 32
+STATUS_ALIGN_TEXT_LONGER, STATUS_DURATION_NEGATIVE, STATUS_SEGMENT_LONGER = 16, 32, 64
 
 _lib = None
 

@@ -173,6 +173,8 @@ int64_t attn_score_elems(int window, int dk, int B, int n_heads, int T);
 
 // standard-normal draws (Philox4x32-10 + Box-Muller); element i depends only on (seed, offset, i)
 int32_t k_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s);
+// uniform draws in [0, 1) on the same counter convention (24-bit mantissas, torch.rand's mapping)
+int32_t k_rand(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s);
 // out = x * mask[b,t]
 int32_t k_mask_rows(const float* x, const float* mask, int B, int C, int T, float* out,
                     hipStream_t s);
@@ -190,5 +192,15 @@ int32_t k_path_to_durations(const int32_t* path, const int32_t* t_ys, const int3
                             float* w, float* cum, int32_t* frame2phone, float* attn, hipStream_t s);
 int32_t k_counts_to_lengths(const int64_t* counts, const float* mask, int B, int T, float* w_ceil, float* cum,
                             int64_t* y_lengths, int32_t* status, hipStream_t s);
+
+// teacher-forced reconstruction (losses.hip): slice ids, the slice gather, the two reductions
+int32_t k_slice_ids(const float* u, const int64_t* ids_in, const int64_t* lengths, int B, int T, int segment,
+                    int64_t* ids, int32_t* status, hipStream_t s);
+int32_t k_slice_segments(const float* x, int64_t x_bs, int64_t x_cs, const int64_t* ids, int B, int C, int T,
+                         int segment, int scale, float* out, hipStream_t s);
+int32_t k_kl_loss(const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, const float* mask,
+                  int B, int I, int T, float weight, float* partials, float* per_utt, float* total, hipStream_t s);
+int32_t k_l1_loss(const float* a, const float* b, int B, int64_t N, float weight, float* partials, float* per_utt,
+                  float* total, hipStream_t s);
 
 }  // namespace wetts

@@ -1382,6 +1382,26 @@ int32_t k_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream
   return WETTS_OK;
 }
 
+// torch.rand (commons.py:54) on the same counters: the low 24 bits of a Philox word times 2^-24 (ATen's uniform_real for
+// float), four values per thread.
+__global__ void rand_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q * 4 >= n) return;
+  const uint64_t ctr = offset + (uint64_t)q;
+  uint32_t r[4];
+  philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (q * 4 + i < n) out[q * 4 + i] = (float)(r[i] & 0xFFFFFFu) * (1.0f / 16777216.0f);
+}
+
+int32_t k_rand(float* out, int64_t n, uint64_t seed, uint64_t offset, hipStream_t s) {
+  if (n <= 0) return WETTS_OK;
+  hipLaunchKernelGGL(rand_kernel, grid1d((n + 3) / 4, 256), dim3(256), 0, s, out, n, seed, offset);
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
 // out[b,c,t] = x[b,c,t] * mask[b,t]   (`z * y_mask` of infer_encoder, models.py:322-331)
 __global__ void mask_rows_kernel(const float* __restrict__ x, const float* __restrict__ mask,
                                  int64_t total, int C, int T, float* __restrict__ out) {

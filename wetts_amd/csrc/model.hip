@@ -1419,6 +1419,11 @@ int32_t wetts_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, void*
   return k_randn(out, n, seed, offset, (hipStream_t)stream);
 }
 
+int32_t wetts_rand(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
+  WETTS_REQUIRE(out != nullptr || n == 0, "null argument");
+  return k_rand(out, n, seed, offset, (hipStream_t)stream);
+}
+
 int32_t wetts_mask_rows(const float* x, const float* mask, int32_t B, int32_t C, int32_t T,
                         float* out, void* stream) {
   WETTS_REQUIRE(x && mask && out, "null argument");

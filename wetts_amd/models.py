@@ -23,7 +23,7 @@ import os
 
 import torch
 
-from . import _lib, checkpoint, config as _config
+from . import _lib, checkpoint, commons, config as _config
 
 
 class _Workspace:
@@ -428,6 +428,16 @@ class SynthesizerTrn:
         deterministic search and ignores it.  An utterance with more phonemes than frames has no monotonic alignment:
         the reference's search returns a meaningless path for it, here the call raises ValueError.  Ids outside their
         tables raise IndexError.  `infer(x, x_lengths, sid, durations=w)` resynthesises with the recording's timing."""
+        x, y, B, Tx, Ty = self._align_args(x, x_lengths, y, y_lengths, sid, eps_q)
+        status, st = self._align_stages(self._require_posterior(), x, x_lengths, y, y_lengths, sid, eps_q, B, Tx, Ty)
+        self.last_status = int(status.cpu().item()) & 0xFFFFFFFF  # the call's one host sync
+        self._align_raise()
+        self._last_align = st
+        return (st["attn"].unsqueeze(1), st["w"].unsqueeze(1), st["x_mask"].unsqueeze(1), st["y_mask"].unsqueeze(1),
+                (st["z"], st["z_p"], st["m_p"], st["logs_p"], st["m_q"], st["logs_q"]))
+
+    def _align_args(self, x, x_lengths, y, y_lengths, sid, eps_q):
+        """The argument checks of align() / reconstruct(), before anything is launched -> (x, y, B, Tx, Ty)."""
         x = torch.as_tensor(x)
         y = torch.as_tensor(y)
         if x.dim() != 2:
@@ -436,15 +446,19 @@ class SynthesizerTrn:
             raise ValueError(f"y must be [{x.shape[0]}, {self.spec_channels}, Ty], got {tuple(y.shape)}")
         B, Tx = x.shape
         Ty = y.shape[2]
-        I = self.inter_channels
         for name, t in (("x_lengths", x_lengths), ("y_lengths", y_lengths)):
             if tuple(torch.as_tensor(t).shape) != (B,):
                 raise ValueError(f"{name} must be [{B}], got {tuple(torch.as_tensor(t).shape)}")
         if self.n_speakers > 0 and sid is None:
             raise ValueError("sid is required when n_speakers > 0")
-        if eps_q is not None and tuple(eps_q.shape) != (B, I, Ty):
-            raise ValueError(f"eps_q must be [{B},{I},{Ty}], got {tuple(eps_q.shape)}")
-        lib = self._require_posterior()
+        if eps_q is not None and tuple(eps_q.shape) != (B, self.inter_channels, Ty):
+            raise ValueError(f"eps_q must be [{B},{self.inter_channels},{Ty}], got {tuple(eps_q.shape)}")
+        return x, y, B, Tx, Ty
+
+    def _align_stages(self, lib, x, x_lengths, y, y_lengths, sid, eps_q, B, Tx, Ty):
+        """The launches of align() on checked arguments, without its read-back -> (status word tensor, stage dict).
+        Shared by align() and reconstruct(); the status word stays readable until the caller fetches it."""
+        I = self.inter_channels
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -498,7 +512,13 @@ class SynthesizerTrn:
                                              _lib.ptr(y_lengths), _lib.ptr(z_p), I * Ty, Ty, 0.0, B, Tx, Ty,
                                              _lib.ptr(f2p_lr), _lib.ptr(y_mask_lr), None, _lib.ptr(m_p),
                                              _lib.ptr(logs_p), _lib.ptr(unused), s), "length_regulate")
-        self.last_status = int(status.cpu().item()) & 0xFFFFFFFF  # the call's one host sync
+        st = dict(g=g, x_enc=x_enc, stats=stats, x_mask=x_mask, y_mask=y_mask, z=z, m_q=m_q, logs_q=logs_q,
+                  z_p=z_p, neg_cent=neg_cent, path=path, t_xs=t_xs, t_ys=t_ys, w=w, cum=cum,
+                  frame2phone=f2p, attn=attn, m_p=m_p, logs_p=logs_p)
+        return status, dict(st, y_lengths=y_lengths)
+
+    def _align_raise(self):
+        """What align() raises from the status word it read back (self.last_status)."""
         if self.last_status & _lib.STATUS_PHONE_ID_RANGE:
             raise IndexError("index out of range in self (phoneme id outside emb, encoders.py:48)")
         if self.last_status & _lib.STATUS_SPEAKER_ID_RANGE:
@@ -506,11 +526,57 @@ class SynthesizerTrn:
         if self.last_status & _lib.STATUS_ALIGN_TEXT_LONGER:
             raise ValueError("align: an utterance has more phonemes than frames (x_lengths[b] > y_lengths[b]); no "
                              "monotonic alignment exists")
-        self._last_align = dict(g=g, x_enc=x_enc, stats=stats, x_mask=x_mask, y_mask=y_mask, z=z, m_q=m_q, logs_q=logs_q,
-                                z_p=z_p, neg_cent=neg_cent, path=path, t_xs=t_xs, t_ys=t_ys, w=w, cum=cum,
-                                frame2phone=f2p, attn=attn, m_p=m_p, logs_p=logs_p)
-        return (attn.unsqueeze(1), w.unsqueeze(1), x_mask.unsqueeze(1), y_mask.unsqueeze(1),
-                (z, z_p, m_p, logs_p, m_q, logs_q))
+
+    # ---- teacher-forced reconstruction (models.py:161-226 without the duration loss) ---------------------------------
+    def reconstruct(self, x, x_lengths, y, y_lengths, sid=None, segment_size=None, ids_slice=None, eps_q=None):
+        """How well the checkpoint reconstructs the recording `y` from its transcript `x`: forward()'s teacher-forced
+        computation without gradients and without the duration loss.  Arguments as align(); returns (o [B,1,segment*hop],
+        ids_slice [B] int64, attn [B,1,Ty,Tx], x_mask, y_mask, (z, z_p, m_p, logs_p, m_q, logs_q)) -- forward()'s tuple
+        without `l_length` and its eighth element.  wetts_amd.losses.teacher_forced_losses turns it into the
+        reconstruction losses of train.py.
+
+        Stages, all on the caller's stream: align()'s stages -> slice ids (commons.rand_slice_segments, models.py:214)
+        -> slice z -> the decoder on the slice with no mask (models.py:216), in the precision set_decoder_dtype
+        selected.  One host read-back per call (the status word, at the end).
+
+        `segment_size` (frames) defaults to the constructor's.  `ids_slice` [B] (optional, not in the reference)
+        gives the slice starts; without it they are drawn as the reference draws them, u * (len - segment + 1)
+        truncated, with u from the Philox kernel under torch.manual_seed, and clamped to len - segment.  `eps_q` as
+        in align().
+
+        segment_size > Ty or a wrong shape raises ValueError before anything is launched; an utterance shorter than
+        the segment, or a given id outside [0, len - segment], raises ValueError after the read-back.  align()'s
+        IndexError / ValueError conditions carry over."""
+        x, y, B, Tx, Ty = self._align_args(x, x_lengths, y, y_lengths, sid, eps_q)
+        seg = int(self.segment_size if segment_size is None else segment_size)
+        if seg < 1 or seg > Ty:
+            raise ValueError(f"segment_size must be in [1, Ty={Ty}], got {seg}")
+        if ids_slice is not None and tuple(torch.as_tensor(ids_slice).shape) != (B,):
+            raise ValueError(f"ids_slice must be [{B}], got {tuple(torch.as_tensor(ids_slice).shape)}")
+        lib = self._require_posterior()
+        status, st = self._align_stages(lib, x, x_lengths, y, y_lengths, sid, eps_q, B, Tx, Ty)
+        I = self.inter_channels
+        s = _lib.current_stream_ptr()
+        ids = torch.empty(B, dtype=torch.int64, device=self.device)
+        u = ids_in = None
+        if ids_slice is None:
+            u = self._rand(B)
+        else:
+            ids_in = self._ids(torch.as_tensor(ids_slice))
+        _lib.check(lib.wetts_slice_ids(_lib.ptr(u), _lib.ptr(ids_in), _lib.ptr(st["y_lengths"]), B, Ty, seg,
+                                       _lib.ptr(ids), _lib.ptr(status), s), "slice_ids")
+        z_slice = torch.empty(B, I, seg, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wetts_slice_segments(_lib.ptr(st["z"]), I * Ty, Ty, _lib.ptr(ids), B, I, Ty, seg, 1,
+                                            _lib.ptr(z_slice), s), "slice_segments")
+        o = self._decode(z_slice, st["g"], None, seg)
+        self.last_status = int(status.cpu().item()) & 0xFFFFFFFF  # the call's one host sync
+        self._align_raise()
+        if self.last_status & _lib.STATUS_SEGMENT_LONGER:
+            raise ValueError(f"reconstruct: an utterance is shorter than the segment of {seg} frames, or a given "
+                             "ids_slice lies outside [0, y_lengths[b] - segment_size]")
+        self._last_recon = dict(st, u=u, ids_slice=ids, z_slice=z_slice, o=o, segment_size=seg)
+        return (o, ids, st["attn"].unsqueeze(1), st["x_mask"].unsqueeze(1), st["y_mask"].unsqueeze(1),
+                (st["z"], st["z_p"], st["m_p"], st["logs_p"], st["m_q"], st["logs_q"]))
 
     # ---- stages ----------------------------------------------------------------------------------
     def _ids(self, t):
@@ -564,6 +630,11 @@ class SynthesizerTrn:
         used = (n + 3) // 4  # Philox counters consumed (4 normals each)
         gen.set_offset(offset + (used + 3) // 4 * 4)  # ATen keeps the offset a multiple of 4
         return out
+
+    def _rand(self, n):
+        """Uniform [0, 1) float32 [n] from the same stream (replaces torch.rand, commons.py:54); see _randn."""
+        self._require()
+        return commons.rand(n, self.device)
 
     # The encoder call in two halves around its one host synchronisation.  Each half is (a) a set of device buffers
     # and (b) stream-ordered launches that touch nothing else -- so a half can also be captured once into a HIP graph
