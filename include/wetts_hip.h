@@ -155,6 +155,15 @@ int32_t wetts_posterior_blob_tensor_info(const wetts_config_t* cfg, int32_t spec
                                          int64_t shape[4]);
 int64_t wetts_posterior_blob_numel(const wetts_config_t* cfg, int32_t spec_channels);
 
+/* The duration posterior's own blob (SynthesizerTrn.duration_loss): what StochasticDurationPredictor.forward(
+ * reverse=False) reads beyond the main blob (duration_predictors.py:176-195) -- dp.flows.1.* (the ConvFlow the reverse
+ * pass drops), dp.post_pre / post_proj / post_convs.* and dp.post_flows.{0,1,3,5,7}.*.  Same conventions as the main
+ * blob; it has no tensors for a use_sdp = 0 config. */
+int32_t wetts_duration_blob_num_tensors(const wetts_config_t* cfg);
+int32_t wetts_duration_blob_tensor_info(const wetts_config_t* cfg, int32_t index, char* name_buf, size_t name_buf_len,
+                                        int64_t* offset, int64_t* numel, int64_t shape[4]);
+int64_t wetts_duration_blob_numel(const wetts_config_t* cfg);
+
 /* ---- model lifetime ---------------------------------------------------------------------- */
 
 /* Builds a model on the CURRENT HIP device from a device-resident blob (e.g. the buffer an
@@ -437,6 +446,76 @@ int32_t wetts_kl_loss(const float* z_p, const float* logs_q, const float* m_p, c
  * Summation order as wetts_kl_loss. */
 int32_t wetts_l1_loss(const float* a, const float* b, int32_t B, int64_t N, float weight, float* partials,
                       float* per_utt, float* total, void* stream);
+
+/* ---- duration loss (models.py:196-206: `l_length` and the logw / logw_ returned with it) ----------------------------- */
+
+/* Set-up call (like wetts_load_posterior_encoder): copies the duration blob (wetts_duration_blob_tensor_info order,
+ * device pointer, may be freed after the call) into the model, packs its convs and returns after `stream` has
+ * drained.  A second call replaces the first.  SDP models only. */
+int32_t wetts_load_duration_posterior(wetts_model_t* m, const float* blob_dev, int64_t numel, void* stream);
+
+/* Scratch of wetts_duration_sdp_forward for B utterances of Tx phonemes. */
+int64_t wetts_duration_loss_workspace_bytes(const wetts_model_t* m, int32_t B, int32_t Tx);
+
+/* StochasticDurationPredictor.forward(x, x_mask, w, g, reverse=False) (duration_predictors.py:206-253; the spline's
+ * forward branch, transforms.py:188-206), f32, no gradients:
+ *   x_enc [B,H,Tx], x_mask [B,Tx], g [B,gin] (may be NULL), w [B,Tx] frame counts, e_q [B,2,Tx] the caller's
+ *   standard-normal draw (torch.randn at :229; masked inside);
+ *   nll[b], logq[b] as at :251-252 and :240-242, both[b] = nll[b] + logq[b] (what the module returns; may be NULL),
+ *   per_utt[b] = both[b] / sum_t x_mask[b] (models.py:199 divides by the whole batch's mask sum instead:
+ *   wetts_duration_loss_total).
+ * Stage outputs, each may be NULL: z_q [B,2,Tx] (the posterior flows' output), z [B,2,Tx] (the main flows' output),
+ * nll_terms / logq_terms [B,Tx]: per position, minus the log-determinants nll resp. logq subtract (the splines, the Log
+ * flow, the two logsigmoids), without the Gaussian terms and ElementwiseAffine's constant -- the accumulators the
+ * reduction reads.  Nothing behind an utterance's length is read from w or e_q; every output is zero there.
+ * A masked-in w that is negative / not finite ORs WETTS_STATUS_DURATION_NEGATIVE / _NONFINITE into status_dev (may be
+ * NULL = the registered word).  No floating-point atomics: results repeat bit for bit, and the reduction of a row
+ * depends on that row alone (order as wetts_kl_loss).  A row with no phoneme under the mask has nll = logq = 0 and
+ * per_utt = NaN (0 / 0), and wetts_duration_loss_total of an all-empty batch divides by zero likewise, as the reference's
+ * `/ torch.sum(x_mask)` does; SynthesizerTrn.duration_loss refuses an empty batch.  Needs
+ * wetts_load_duration_posterior first. */
+int32_t wetts_duration_sdp_forward(const wetts_model_t* m, const float* x_enc, const float* x_mask, const float* g,
+                                   const float* w, const float* e_q, int32_t B, int32_t Tx, float* nll, float* logq,
+                                   float* both, float* per_utt, float* z_q, float* z, float* nll_terms, float* logq_terms,
+                                   int32_t* status_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The reduction at the end of wetts_duration_sdp_forward on given stage tensors (z, e_q [B,2,Tx], the two term
+ * tensors [B,Tx]): nll, logq, both = nll + logq, per_utt [B]. */
+int32_t wetts_duration_reduce(const wetts_model_t* m, const float* nll_terms, const float* logq_terms, const float* z,
+                              const float* e_q, const float* x_mask, int32_t B, int32_t Tx, float* nll, float* logq,
+                              float* both, float* per_utt, void* stream);
+
+/* DurationPredictor models (models.py:201-206): logw_target = log(w + 1e-6) * x_mask [B,Tx], rows[b] = sum_t (logw -
+ * logw_target)^2, per_utt[b] = rows[b] / sum_t x_mask[b].  Status bits as above, into the registered word. */
+int32_t wetts_duration_dp_loss(const wetts_model_t* m, const float* logw, const float* w, const float* x_mask,
+                               int32_t B, int32_t Tx, float* logw_target, float* rows, float* per_utt, void* stream);
+
+/* logw_target = log(w + 1e-6) * x_mask [B,Tx] alone (models.py:201, SDP models); nothing behind a length is read. */
+int32_t wetts_duration_logw_target(const float* w, const float* x_mask, int32_t B, int32_t Tx, float* logw_target,
+                                   void* stream);
+
+/* Validation aids: the elementwise steps of wetts_duration_sdp_forward on given device tensors, no model needed.
+ *   affine_forward: ElementwiseAffine forward, out [B,2,Tx] = (m + exp(logs) * (x * mask)) * mask; m, logs [2].
+ *   spline_forward: one ConvFlow's spline on z [B,2,Tx] in place (channel ch0 *= mask, channel 1 - ch0 transformed) with
+ *     h [B,29,Tx] the flow's projection, div = sqrt(filter_channels); acc [B,Tx] += sign * logabsdet * mask.
+ *   dequant_log: z_q [B,2,Tx] (z_u at channel chu), w [B,Tx] -> z [B,2,Tx], nll_terms / logq_terms [B,Tx] accumulated.
+ *   pre: post_pre, out [B,C,Tx] = weight[c] * (w under the mask) + bias[c].
+ * Every one is a function of its own (b, t) alone: a row gives the same bits alone and inside a batch. */
+int32_t wetts_duration_affine_forward(const float* x, const float* m, const float* logs, const float* x_mask, int32_t B,
+                                      int32_t Tx, float* out, void* stream);
+int32_t wetts_duration_spline_forward(float* z, int32_t ch0, const float* h, const float* x_mask, float div, int32_t B,
+                                      int32_t Tx, float sign, float* acc, void* stream);
+int32_t wetts_duration_dequant_log(const float* z_q, int32_t chu, const float* w, const float* x_mask, int32_t B,
+                                   int32_t Tx, float* z, float* nll_terms, float* logq_terms, int32_t* status_dev,
+                                   void* stream);
+int32_t wetts_duration_pre(const float* w, const float* x_mask, const float* weight, const float* bias, int32_t B,
+                           int32_t C, int32_t Tx, float* out, void* stream);
+
+/* models.py:199 / :206 and train.py:485: l_length[b] = per_row[b] / sum(x_mask) with the sum over the WHOLE batch,
+ * total[0] = sum_b l_length[b] (`loss_dur = torch.sum(l_length.float())`), total[1] = weight * total[0].  One wave, fixed
+ * order.  per_row: nll + logq per utterance (SDP) or wetts_duration_dp_loss's rows. */
+int32_t wetts_duration_loss_total(const float* per_row, const float* x_mask, int32_t B, int32_t Tx, float weight,
+                                  float* l_length, float* total, void* stream);
 
 /* a16 inference.py:100-110 output scaling: per utterance peak-normalise to 0.6 full scale,
  * clip, convert to int16.  lengths_samples [B] int64 = valid samples per row (peak is taken

@@ -99,6 +99,22 @@ SIGNATURES = {
     "wetts_slice_segments": (_I32, [_P, _I64, _I64, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "wetts_kl_loss": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
     "wetts_l1_loss": (_I32, [_P, _P, _I32, _I64, _F, _P, _P, _P, _P]),
+    "wetts_duration_blob_num_tensors": (_I32, [_CFG]),
+    "wetts_duration_blob_tensor_info": (_I32, [_CFG, _I32, C.c_char_p, C.c_size_t, C.POINTER(_I64), C.POINTER(_I64),
+                                               C.POINTER(_I64 * 4)]),
+    "wetts_duration_blob_numel": (_I64, [_CFG]),
+    "wetts_load_duration_posterior": (_I32, [_P, _P, _I64, _P]),
+    "wetts_duration_loss_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_duration_sdp_forward": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                          _I64, _P]),
+    "wetts_duration_reduce": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "wetts_duration_dp_loss": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "wetts_duration_logw_target": (_I32, [_P, _P, _I32, _I32, _P, _P]),
+    "wetts_duration_affine_forward": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "wetts_duration_spline_forward": (_I32, [_P, _I32, _P, _P, _F, _I32, _I32, _F, _P, _P]),
+    "wetts_duration_dequant_log": (_I32, [_P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "wetts_duration_pre": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
+    "wetts_duration_loss_total": (_I32, [_P, _P, _I32, _I32, _F, _P, _P, _P]),
     "wetts_stft_basis_numel": (_I64, [_I32, _I32]),
     "wetts_stft_basis": (_I32, [_I32, _I32, _P, _I64, _P]),
     "wetts_spectrogram": (_I32, [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _P]),

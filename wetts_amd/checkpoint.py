@@ -151,6 +151,57 @@ def pack_posterior_blob(cfg, spec_channels, state_dict):
     return blob
 
 
+def duration_layout(cfg):
+    """[(name, offset, numel, shape)] of the duration posterior's own blob (SynthesizerTrn.duration_loss): `dp.flows.1.*`,
+    `dp.post_pre`, `dp.post_proj`, `dp.post_convs.*`, `dp.post_flows.*`, as the library defines it
+    (wetts_duration_blob_tensor_info).  Empty for a DurationPredictor model (use_sdp = false)."""
+    lib = _lib.load()
+    n = lib.wetts_duration_blob_num_tensors(C.byref(cfg))
+    if n < 0:
+        raise _lib.WettsError(f"invalid config: {_lib.last_error()}")
+    out = []
+    buf = C.create_string_buffer(256)
+    off, num, shape = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+    for i in range(n):
+        _lib.check(lib.wetts_duration_blob_tensor_info(C.byref(cfg), i, buf, 256, C.byref(off), C.byref(num),
+                                                       C.byref(shape)), "duration_blob_tensor_info")
+        shp = tuple(int(s) for s in shape if s > 0)
+        out.append((buf.value.decode(), int(off.value), int(num.value), shp))
+    return out
+
+
+def duration_numel(cfg):
+    n = _lib.load().wetts_duration_blob_numel(C.byref(cfg))
+    if n < 0:
+        raise _lib.WettsError(f"invalid config: {_lib.last_error()}")
+    return int(n)
+
+
+def has_duration(cfg, state_dict):
+    """True when `state_dict` carries every tensor of the duration layout (and the layout has any: SDP models)."""
+    lay = duration_layout(cfg)
+    return bool(lay) and all(name in state_dict for name, _, _, _ in lay)
+
+
+def pack_duration_blob(cfg, state_dict):
+    """Natural-layout float32 CPU blob of the duration posterior from a reference-keyed state_dict.  Every tensor must be
+    present (there is no init value to fall back to) and have its layout shape."""
+    blob = torch.zeros(duration_numel(cfg), dtype=torch.float32)
+    missing = []
+    for name, off, numel, shape in duration_layout(cfg):
+        t = state_dict.get(name)
+        if t is None:
+            missing.append(name)
+            continue
+        t = t.detach().to(torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != expected {shape}")
+        blob[off:off + numel] = t.reshape(-1)
+    if missing:
+        raise KeyError(f"{len(missing)} duration predictor tensors missing from checkpoint: {missing}")
+    return blob
+
+
 def load_state_dict_file(checkpoint_path):
     """Reads `G_*.pth` as saved by task.save_checkpoint (task.py:59-76): {"model": state_dict,
     "iteration", "optimizer", "learning_rate"}; a bare state_dict is accepted too."""

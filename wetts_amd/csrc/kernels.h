@@ -64,6 +64,32 @@ int32_t k_spline_inverse(float* z, int ch0, int ch1, const float* h, const float
 int32_t k_affine_reverse(const float* z, int ch, const float* m, const float* logs, int param_idx,
                          const float* mask, int B, int T, float* logw, hipStream_t s);
 
+// ---- duration loss (duration_loss.hip): StochasticDurationPredictor.forward(reverse=False), DurationPredictor MSE ----
+// ElementwiseAffine forward on both channels of x [B,2,T] (read under the mask) -> out (may alias x)
+int32_t k_affine_forward(const float* x, const float* m, const float* logs, const float* mask, int B, int T,
+                         float* out, hipStream_t s);
+// Rational-quadratic spline forward with linear tails + cat + mask (transforms.py:47-147,188-207): z [B,2,T] in place
+// like k_spline_inverse; acc [B,T] += sign * logabsdet * mask.  num_bins must be 10.
+int32_t k_spline_forward(float* z, int ch0, int ch1, const float* h, const float* mask, int num_bins, float tail_bound,
+                         float div, int B, int T, float sign, float* acc, hipStream_t s);
+// dequantisation + Log flow (duration_predictors.py:235-247): z_q [B,2,T] (z_u at channel chu, z1 at ch1), w [B,T] ->
+// z [B,2,T] = cat(log(clamp_min(w - sigmoid(z_u), 1e-5)), z1) * mask, and the two accumulators' terms
+int32_t k_dequant_log(const float* z_q, int chu, int ch1, const float* w, const float* mask, int B, int T, float* z,
+                      float* nll_terms, float* logq_terms, int32_t* status, hipStream_t s);
+// post_pre: Conv1d(1, C, 1) of w [B,T] read under the mask -> out [B,C,T]
+int32_t k_duration_pre(const float* w, const float* mask, const float* wt, const float* bias, int B, int C, int T,
+                       float* out, hipStream_t s);
+int32_t k_duration_add(const float* a, const float* b, int64_t n, float* out, hipStream_t s);
+// out[b,c,t] = src[b, c ^ swapped, t] on [B,2,T]
+int32_t k_duration_unswap(const float* src, int swapped, int B, int T, float* out, hipStream_t s);
+// per-utterance nll / logq / their sum / the sum over the utterance's length, in the fixed order of losses.hip
+int32_t k_duration_reduce(const float* nll_terms, const float* logq_terms, const float* z, const float* e_q,
+                          const float* mask, const float* logs, const float* qlogs, int B, int T, float* nll,
+                          float* logq, float* both, float* per_utt, hipStream_t s);
+// DurationPredictor: target = log(w + 1e-6) * mask, rows[b] = sum_t (logw - target)^2, per_utt[b] = rows[b] / len
+int32_t k_dp_mse(const float* logw, const float* w, const float* mask, int B, int T, float* target, float* rows,
+                 float* per_utt, int32_t* status, hipStream_t s);
+
 // commons.fused_add_tanh_sigmoid_multiply (commons.py:98-105): a [B,2H,T] -> out [B,H,T]
 int32_t k_gate(const float* a, int B, int H, int T, float* out, hipStream_t s);
 

@@ -187,6 +187,13 @@ static void add_dds(Layout& L, const std::string& p, int C, int k, int n) {
   }
 }
 
+// ConvFlow(2, C, 3, n_layers=3) under `p` (duration_predictors.py:80-86): num_bins = 10, so proj has 3 * 10 - 1 rows
+static void add_convflow(Layout& L, const std::string& p, int C) {
+  L.add_conv(p + ".pre", C, 1, 1);
+  add_dds(L, p + ".convs", C, 3, 3);
+  L.add_conv(p + ".proj", 29, C, 1);
+}
+
 // One conv of the HiFi-GAN generator (decoders.py:15-88), in checkpoint order
 struct GenConv {
   enum Kind { PRE, UP, C1, C2, POST, COND } kind;
@@ -247,12 +254,7 @@ static void build_layout(const wetts_config_t* c, Layout& L) {
     L.add("dp.flows.0.m", 2, 1);
     L.add("dp.flows.0.logs", 2, 1);
     // flows = [EA, CF1, Flip, CF2, Flip, ...]; reverse drops CF1 (duration_predictors.py:255-256)
-    for (int f = 1; f < c->sdp_n_flows; ++f) {
-      std::string p = S("dp.flows.%d", 2 * f + 1);
-      L.add_conv(p + ".pre", C, 1, 1);
-      add_dds(L, p + ".convs", C, 3, 3);
-      L.add_conv(p + ".proj", 29, C, 1);
-    }
+    for (int f = 1; f < c->sdp_n_flows; ++f) add_convflow(L, S("dp.flows.%d", 2 * f + 1), C);
   } else {
     const int Fd = c->dp_filter_channels;
     L.add_conv("dp.conv_1", Fd, H, 3, 1, 1);
@@ -318,6 +320,24 @@ static void build_posterior_layout(const wetts_config_t* c, int spec, Layout& L)
   // WN builds cond_layer whenever gin_channels != 0 (modules.py:35-36)
   add_wn(L, "enc_q.enc", H, kPostKernel, kPostLayers, c->gin_channels);
   L.add_conv("enc_q.proj", 2 * I, H, 1);
+}
+
+// What StochasticDurationPredictor.forward(reverse=False) reads beyond the main blob (duration_predictors.py:176-195,
+// 225-250): the first ConvFlow of `flows`, which the reverse pass drops as useless, and the posterior of the
+// dequantisation noise -- post_pre, post_proj, post_convs, post_flows = [ElementwiseAffine, (ConvFlow, Flip) x 4].  A blob
+// of their own (wetts_load_duration_posterior), so the main blob stays as it is.  Empty for use_sdp = 0.
+constexpr int kPostFlows = 4;
+
+static void build_duration_layout(const wetts_config_t* c, Layout& L) {
+  if (!c->use_sdp) return;
+  const int C = c->hidden_channels;
+  add_convflow(L, "dp.flows.1", C);
+  L.add_conv("dp.post_pre", C, 1, 1);
+  L.add_conv("dp.post_proj", C, C, 1);
+  add_dds(L, "dp.post_convs", C, 3, 3);
+  L.add("dp.post_flows.0.m", 2, 1);
+  L.add("dp.post_flows.0.logs", 2, 1);
+  for (int f = 0; f < kPostFlows; ++f) add_convflow(L, S("dp.post_flows.%d", 2 * f + 1), C);
 }
 
 static int validate_posterior(const wetts_config_t* c, int spec) {
@@ -495,6 +515,17 @@ struct wetts_model {
   PackedConv pe_pre, pe_proj;
   std::vector<PackedConv> pe_in, pe_rs, fwd_pre;
   const float *pe_cond_w = nullptr, *pe_cond_b = nullptr;
+
+  // duration posterior (wetts_duration_sdp_forward), built by wetts_load_duration_posterior from a blob of its own
+  bool dur_loaded = false;
+  Layout dur_layout;
+  float* dur_blob = nullptr;
+  ConvFlowW dur_cf1;                   // dp.flows.1
+  std::vector<ConvFlowW> dur_post_cf;  // dp.post_flows.{1,3,5,7}
+  const float *dur_post_pre_w = nullptr, *dur_post_pre_b = nullptr;
+  PackedConv dur_post_proj;
+  DDS dur_post_dds;
+  const float *dur_qm = nullptr, *dur_qlogs = nullptr;  // dp.post_flows.0
 
   const float* T(const std::string& name) const { return tensor(layout, blob, name); }
 };
@@ -881,6 +912,36 @@ static void free_posterior(wetts_model* m) {
   m->post_loaded = false;
 }
 
+static void free_dds(DDS* d) {
+  for (int i = 0; i < 3; ++i) free_packed(&d->c1x1[i]);
+}
+
+static void free_convflow(ConvFlowW* cf) {
+  free_dds(&cf->dds);
+  free_packed(&cf->proj);
+}
+
+static void free_duration(wetts_model* m) {
+  free_convflow(&m->dur_cf1);
+  m->dur_cf1 = ConvFlowW();
+  for (ConvFlowW& cf : m->dur_post_cf) free_convflow(&cf);
+  m->dur_post_cf.clear();
+  free_packed(&m->dur_post_proj);
+  free_dds(&m->dur_post_dds);
+  m->dur_post_dds = DDS();
+  if (m->dur_blob) (void)hipFree(m->dur_blob);
+  m->dur_blob = nullptr;
+  m->dur_post_pre_w = m->dur_post_pre_b = m->dur_qm = m->dur_qlogs = nullptr;
+  m->dur_layout = Layout();
+  m->dur_loaded = false;
+}
+
+// scratch of wetts_duration_sdp_forward: the reverse pass's buffers, x + h_w, both flow states and the two accumulators
+static int64_t ws_duration(const wetts_config_t* c, int B, int Tx) {
+  const int64_t H = c->hidden_channels;
+  return 6 * A256(B * H * Tx) + A256(B * 32 * Tx) + 2 * A256(B * 2 * Tx) + 2 * A256(B * Tx) + A256(B * H) + A256(B) + 256;
+}
+
 // scratch of wetts_posterior_encoder: mask rows, h, the f32 WN buffers, cond_layer output, stats
 static int64_t ws_posterior(const wetts_config_t* c, int B, int Ty_) {
   const int64_t H = c->hidden_channels, I = c->inter_channels;
@@ -959,6 +1020,36 @@ int64_t wetts_posterior_blob_numel(const wetts_config_t* cfg, int32_t spec_chann
   if (validate_posterior(cfg, spec_channels) != WETTS_OK) return WETTS_E_INVALID;
   Layout L;
   build_posterior_layout(cfg, spec_channels, L);
+  return L.total;
+}
+
+int32_t wetts_duration_blob_num_tensors(const wetts_config_t* cfg) {
+  if (validate_config(cfg) != WETTS_OK) return WETTS_E_INVALID;
+  Layout L;
+  build_duration_layout(cfg, L);
+  return (int32_t)L.specs.size();
+}
+
+int32_t wetts_duration_blob_tensor_info(const wetts_config_t* cfg, int32_t index, char* name_buf, size_t name_buf_len,
+                                        int64_t* offset, int64_t* numel, int64_t shape[4]) {
+  WETTS_TRY(validate_config(cfg));
+  Layout L;
+  build_duration_layout(cfg, L);
+  WETTS_REQUIRE(index >= 0 && index < (int32_t)L.specs.size(), "tensor index %d out of range", index);
+  const TensorSpec& t = L.specs[index];
+  WETTS_REQUIRE(name_buf && name_buf_len > t.name.size(), "name buffer too small");
+  strcpy(name_buf, t.name.c_str());
+  if (offset) *offset = t.offset;
+  if (numel) *numel = t.numel;
+  if (shape)
+    for (int i = 0; i < 4; ++i) shape[i] = t.shape[i];
+  return WETTS_OK;
+}
+
+int64_t wetts_duration_blob_numel(const wetts_config_t* cfg) {
+  if (validate_config(cfg) != WETTS_OK) return WETTS_E_INVALID;
+  Layout L;
+  build_duration_layout(cfg, L);
   return L.total;
 }
 
@@ -1057,6 +1148,7 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
 void wetts_destroy(wetts_model_t* m) {
   if (!m) return;
   free_posterior(m);
+  free_duration(m);
   for (PackedConv* pc : m->all_packed) free_packed(pc);
   for (auto& pc : m->b_ups) free_packed_bf16(&pc);
   for (auto& v : m->b_c1) for (auto& pc : v) free_packed_bf16(&pc);
@@ -1389,6 +1481,199 @@ int32_t wetts_duration_dp(const wetts_model_t* m, const float* x_enc, const floa
     WETTS_TRY(launch_conv(m->dp_proj, p, s));
   }
   return WETTS_OK;
+}
+
+namespace wetts {
+static int32_t pack_dds(const Layout& L, const float* blob, const std::string& p, hipStream_t s, DDS* d) {
+  for (int i = 0; i < 3; ++i) {
+    d->sep_w[i] = tensor(L, blob, p + S(".convs_sep.%d.weight", i));
+    d->sep_b[i] = tensor(L, blob, p + S(".convs_sep.%d.bias", i));
+    d->n1g[i] = tensor(L, blob, p + S(".norms_1.%d.gamma", i));
+    d->n1b[i] = tensor(L, blob, p + S(".norms_1.%d.beta", i));
+    d->n2g[i] = tensor(L, blob, p + S(".norms_2.%d.gamma", i));
+    d->n2b[i] = tensor(L, blob, p + S(".norms_2.%d.beta", i));
+    WETTS_TRY(pack(L, blob, p + S(".convs_1x1.%d", i), s, &d->c1x1[i]));
+  }
+  return WETTS_OK;
+}
+
+static int32_t pack_convflow(const Layout& L, const float* blob, const std::string& p, hipStream_t s, ConvFlowW* cf) {
+  cf->pre_w = tensor(L, blob, p + ".pre.weight");
+  cf->pre_b = tensor(L, blob, p + ".pre.bias");
+  WETTS_TRY(pack_dds(L, blob, p + ".convs", s, &cf->dds));
+  return pack(L, blob, p + ".proj", s, &cf->proj);
+}
+
+static int32_t build_duration(wetts_model* m, const float* blob_dev, int64_t numel, hipStream_t s) {
+  build_duration_layout(&m->cfg, m->dur_layout);
+  const Layout& DL = m->dur_layout;
+  WETTS_REQUIRE(numel == DL.total, "duration blob has %lld floats, layout needs %lld", (long long)numel,
+                (long long)DL.total);
+  WETTS_HIP_CHECK(hipMalloc((void**)&m->dur_blob, (size_t)numel * sizeof(float)));
+  WETTS_HIP_CHECK(hipMemcpyAsync(m->dur_blob, blob_dev, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const float* blob = m->dur_blob;
+  WETTS_TRY(pack_convflow(DL, blob, "dp.flows.1", s, &m->dur_cf1));
+  m->dur_post_pre_w = tensor(DL, blob, "dp.post_pre.weight");
+  m->dur_post_pre_b = tensor(DL, blob, "dp.post_pre.bias");
+  WETTS_TRY(pack(DL, blob, "dp.post_proj", s, &m->dur_post_proj));
+  WETTS_TRY(pack_dds(DL, blob, "dp.post_convs", s, &m->dur_post_dds));
+  m->dur_qm = tensor(DL, blob, "dp.post_flows.0.m");
+  m->dur_qlogs = tensor(DL, blob, "dp.post_flows.0.logs");
+  m->dur_post_cf.resize(kPostFlows);
+  for (int f = 0; f < kPostFlows; ++f)
+    WETTS_TRY(pack_convflow(DL, blob, S("dp.post_flows.%d", 2 * f + 1), s, &m->dur_post_cf[f]));
+  return WETTS_OK;
+}
+
+// ConvFlow.forward(reverse=False) (duration_predictors.py:90-120) on z [B,2,T] in place: logical channel c lives at
+// physical channel c ^ swapped; the spline's log-determinant is subtracted from acc [B,T]
+static int32_t run_convflow_forward(const wetts_model* m, const ConvFlowW& cf, float* z, int swapped, const float* g,
+                                    const float* x_mask, int B, int H, int T, float* hh, float* t1, float* t2,
+                                    float* hp, float* acc, hipStream_t s) {
+  const int ch0 = 0 ^ swapped, ch1 = 1 ^ swapped;
+  WETTS_TRY(k_convflow_pre(z, ch0, cf.pre_w, cf.pre_b, g, B, H, T, hh, s));
+  float* hho = hh;
+  WETTS_TRY(run_dds(m, cf.dds, hh, x_mask, B, H, T, t1, t2, s, &hho));
+  ConvParams p = conv_io(hho, H, T, hp, 29, B);  // h = proj(h) * x_mask
+  p.out_mask = x_mask;
+  p.out_mask_stride = T;
+  WETTS_TRY(launch_conv(cf.proj, p, s));
+  return k_spline_forward(z, ch0, ch1, hp, x_mask, 10, 5.0f, (float)sqrt((double)H), B, T, -1.0f, acc, s);
+}
+}  // namespace wetts
+
+int32_t wetts_load_duration_posterior(wetts_model_t* m, const float* blob_dev, int64_t numel, void* stream) {
+  WETTS_REQUIRE(m && blob_dev, "null argument");
+  WETTS_REQUIRE(m->cfg.use_sdp, "model was built with use_sdp=false: the DurationPredictor loss needs no extra tensors");
+  hipStream_t s = (hipStream_t)stream;
+  // a reload replaces the previous copy; the caller has synchronised the streams that used it (set-up call)
+  free_duration(m);
+  int32_t r = build_duration(m, blob_dev, numel, s);
+  if (r == WETTS_OK) {
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      set_error("duration posterior weight packing failed: %s", hipGetErrorString(e));
+      r = WETTS_E_HIP;
+    }
+  }
+  if (r != WETTS_OK) {
+    free_duration(m);
+    return r;
+  }
+  m->dur_loaded = true;
+  return WETTS_OK;
+}
+
+int64_t wetts_duration_loss_workspace_bytes(const wetts_model_t* m, int32_t B, int32_t Tx) {
+  if (!m || B < 0 || Tx < 0) return WETTS_E_INVALID;
+  return ws_duration(&m->cfg, B, Tx) + 4096;
+}
+
+int32_t wetts_duration_sdp_forward(const wetts_model_t* m, const float* x_enc, const float* x_mask, const float* g,
+                                   const float* w, const float* e_q, int32_t B, int32_t Tx, float* nll, float* logq,
+                                   float* both_out, float* per_utt, float* z_q_out, float* z_out, float* nll_terms_out,
+                                   float* logq_terms_out, int32_t* status_dev, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  WETTS_REQUIRE(m && x_enc && x_mask && w && e_q && nll && logq && per_utt, "null argument");
+  WETTS_REQUIRE(m->cfg.use_sdp, "model was built with use_sdp=false");
+  WETTS_REQUIRE(m->dur_loaded, "duration posterior not loaded: call wetts_load_duration_posterior first");
+  WETTS_REQUIRE(B >= 0 && Tx >= 0, "bad shape");
+  SmallConvScope small_scope(m->small_max_tiles);
+  if (B == 0 || Tx == 0) return WETTS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const wetts_config_t* c = &m->cfg;
+  const int H = c->hidden_channels;
+  const int64_t BT = (int64_t)B * Tx;
+  Bump ws(workspace, workspace_bytes);
+  float* xd = ws.take<float>(BT * H);
+  float* t1 = ws.take<float>(BT * H);
+  float* t2 = ws.take<float>(BT * H);
+  float* hh = ws.take<float>(BT * H);
+  float* xg = ws.take<float>(BT * H);
+  float* xh = ws.take<float>(BT * H);
+  float* hp = ws.take<float>(BT * 32);
+  float* zq = ws.take<float>(BT * 2);
+  float* z = ws.take<float>(BT * 2);
+  float* nt = ws.take<float>(BT);
+  float* qt = ws.take<float>(BT);
+  float* cond = ws.take<float>((int64_t)B * H);
+  // [B] scratch for nll + logq
+  float* both = ws.take<float>(B);
+  if (!ws.ok) {
+    set_error("duration_sdp_forward: workspace too small");
+    return WETTS_E_WORKSPACE;
+  }
+  if (!status_dev) status_dev = m->status_word;
+  // the caller's stage buffers double as the accumulators
+  if (nll_terms_out) nt = nll_terms_out;
+  if (logq_terms_out) qt = logq_terms_out;
+  if (both_out) both = both_out;
+  WETTS_HIP_CHECK(hipMemsetAsync(nt, 0, (size_t)BT * sizeof(float), s));
+  WETTS_HIP_CHECK(hipMemsetAsync(qt, 0, (size_t)BT * sizeof(float), s));
+  // x = proj(convs(pre(x) + cond(g))) * mask  (:214-219, as wetts_duration_sdp)
+  {
+    ConvParams p = conv_io(x_enc, H, Tx, xd, H, B);
+    if (has_g(c) && g) {
+      WETTS_TRY(k_cond_linear(g, m->dp_cond_w, m->dp_cond_b, B, H, c->gin_channels, cond, s));
+      p.bias_b = cond;
+      p.bias_b_stride = H;
+    }
+    WETTS_TRY(launch_conv(m->sdp_pre, p, s));
+  }
+  float* xdo = xd;
+  WETTS_TRY(run_dds(m, m->sdp_dds, xd, x_mask, B, H, Tx, t1, t2, s, &xdo));
+  {
+    ConvParams p = conv_io(xdo, H, Tx, xg, H, B);
+    p.out_mask = x_mask;
+    p.out_mask_stride = Tx;
+    WETTS_TRY(launch_conv(m->sdp_proj, p, s));
+  }
+  // h_w = post_proj(post_convs(post_pre(w))) * mask  (:226-228); xh = x + h_w, the posterior flows' g
+  WETTS_TRY(k_duration_pre(w, x_mask, m->dur_post_pre_w, m->dur_post_pre_b, B, H, Tx, xd, s));
+  xdo = xd;
+  WETTS_TRY(run_dds(m, m->dur_post_dds, xd, x_mask, B, H, Tx, t1, t2, s, &xdo));
+  {
+    ConvParams p = conv_io(xdo, H, Tx, hh, H, B);
+    p.out_mask = x_mask;
+    p.out_mask_stride = Tx;
+    WETTS_TRY(launch_conv(m->dur_post_proj, p, s));
+  }
+  WETTS_TRY(k_duration_add(xg, hh, BT * H, xh, s));
+  // z_q = post_flows(e_q * mask): ElementwiseAffine, then (ConvFlow, Flip) x 4  (:229-234)
+  WETTS_TRY(k_affine_forward(e_q, m->dur_qm, m->dur_qlogs, x_mask, B, Tx, zq, s));
+  int swapped = 0;  // logical channel c lives at physical channel c ^ swapped
+  for (int f = 0; f < kPostFlows; ++f) {
+    WETTS_TRY(run_convflow_forward(m, m->dur_post_cf[f], zq, swapped, xh, x_mask, B, H, Tx, hh, t1, t2, hp, qt, s));
+    swapped ^= 1;  // Flip
+  }
+  if (z_q_out) WETTS_TRY(k_duration_unswap(zq, swapped, B, Tx, z_q_out, s));
+  // u, z0 = (w - u), the two logsigmoids, the Log flow, z = cat(z0, z1)  (:235-247)
+  WETTS_TRY(k_dequant_log(zq, 0 ^ swapped, 1 ^ swapped, w, x_mask, B, Tx, z, nt, qt, status_dev, s));
+  // z = flows(z): ElementwiseAffine, then (ConvFlow, Flip) x sdp_n_flows, the first one dp.flows.1  (:248-250)
+  WETTS_TRY(k_affine_forward(z, m->ea_m, m->ea_logs, x_mask, B, Tx, z, s));
+  swapped = 0;
+  for (int f = 0; f < c->sdp_n_flows; ++f) {
+    const ConvFlowW& cf = f == 0 ? m->dur_cf1 : m->cflows[f - 1];
+    WETTS_TRY(run_convflow_forward(m, cf, z, swapped, xg, x_mask, B, H, Tx, hh, t1, t2, hp, nt, s));
+    swapped ^= 1;
+  }
+  if (z_out) WETTS_TRY(k_duration_unswap(z, swapped, B, Tx, z_out, s));
+  return k_duration_reduce(nt, qt, z, e_q, x_mask, m->ea_logs, m->dur_qlogs, B, Tx, nll, logq, both, per_utt, s);
+}
+
+int32_t wetts_duration_reduce(const wetts_model_t* m, const float* nll_terms, const float* logq_terms, const float* z,
+                              const float* e_q, const float* x_mask, int32_t B, int32_t Tx, float* nll, float* logq,
+                              float* both, float* per_utt, void* stream) {
+  WETTS_REQUIRE(m && nll_terms && logq_terms && z && e_q && x_mask && nll && logq && both && per_utt, "null argument");
+  WETTS_REQUIRE(m->cfg.use_sdp && m->dur_loaded, "duration posterior not loaded");
+  return k_duration_reduce(nll_terms, logq_terms, z, e_q, x_mask, m->ea_logs, m->dur_qlogs, B, Tx, nll, logq, both,
+                           per_utt, (hipStream_t)stream);
+}
+
+int32_t wetts_duration_dp_loss(const wetts_model_t* m, const float* logw, const float* w, const float* x_mask,
+                               int32_t B, int32_t Tx, float* logw_target, float* rows, float* per_utt, void* stream) {
+  WETTS_REQUIRE(m && logw && w && x_mask && logw_target && rows && per_utt, "null argument");
+  return k_dp_mse(logw, w, x_mask, B, Tx, logw_target, rows, per_utt, m->status_word, (hipStream_t)stream);
 }
 
 int32_t wetts_durations_to_lengths(const float* logw, const float* x_mask, float length_scale,

@@ -1,12 +1,14 @@
-"""The two reconstruction losses of the reference's training loop (losses.kl_loss, losses.py:45-60, and the mel L1 of
-train.py:486) as evaluation metrics on the device, and `teacher_forced_losses`, which does for one batch what
-train.py:400-432,486-488 does with SynthesizerTrn.reconstruct() in the place of forward().  No gradients; torch
-allocates and takes views, the arithmetic is the HIP kernels of csrc/losses.hip.
+"""The generator-side losses of the reference's training loop that need no discriminator (losses.kl_loss,
+losses.py:45-60, the mel L1 of train.py:486 and the duration loss of train.py:485) as evaluation metrics on the device,
+and `teacher_forced_losses`, which does for one batch what train.py:400-432,485-488 does with
+SynthesizerTrn.reconstruct() and SynthesizerTrn.duration_loss()'s stages in the place of forward().  No gradients; torch
+allocates and takes views, the arithmetic is the HIP kernels of csrc/losses.hip and csrc/duration_loss.hip.
 
 Every sum is formed in a fixed order without floating-point atomics (csrc/losses.hip): results repeat bit for bit, and
 an utterance's per-utterance value is the same alone and inside a padded batch, which is what makes it usable for
-finding the bad transcript or the clipped recording in a corpus.  The stochastic duration predictor's NLL and the
-DurationPredictor's MSE (`l_length`, models.py:198-207) are out of scope.
+finding the bad transcript or the clipped recording in a corpus.  The duration loss (`l_length`, models.py:198-207: the
+stochastic duration predictor's nll + logq, or the DurationPredictor's squared error) divides by the whole batch's
+phoneme count as the reference does; `dur_per_utt` is each utterance's own sum over its own phoneme count.
 """
 import torch
 
@@ -87,7 +89,8 @@ def _flag(section, key):
     return key in section.keys() and bool(section[key])
 
 
-def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None, **reconstruct_kwargs):
+def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None, with_duration=False, e_q=None,
+                          eps_w=None, **reconstruct_kwargs):
     """train.py:400-432,486-488 for one batch, without gradients: net_g.reconstruct(...) in the place of net_g(...), the
     target mel (`spec` itself for a mel posterior encoder, else spec_to_mel_torch(spec)) sliced at ids_slice, the mel
     spectrogram of the decoded slice, and
@@ -98,7 +101,13 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
     Returns a dict of device tensors: loss_mel, loss_kl (weighted scalars), mel, kl (unweighted scalars), mel_per_utt,
     kl_per_utt [B] (unweighted; an utterance's value does not depend on the batch it is scored in), y_hat
     [B, 1, segment * hop], ids_slice [B], y_mel and y_hat_mel [B, n_mel, segment].  The weights are applied by the
-    reduction kernels (their `weight` argument), so no torch arithmetic runs."""
+    reduction kernels (their `weight` argument), so no torch arithmetic runs.
+
+    `with_duration=True` adds the duration loss of train.py:485 on the alignment reconstruct() found: the duration
+    predictor's stages of SynthesizerTrn.duration_loss() on reconstruct()'s own w, x_enc, x_mask and g (no second text
+    encoder pass; `e_q` / `eps_w` [B,2,Tx] inject its draws), and the entries loss_dur (sum_b l_length[b], weighted by
+    hps.train.c_dur where the recipe has one, else 1), dur (unweighted) and dur_per_utt [B].  It costs one more
+    read-back of the status word."""
     d = hps.data
     if int(net_g.hop_length) != int(d.hop_length):
         raise ValueError(f"the model produces {net_g.hop_length} samples per frame but hps.data.hop_length is "
@@ -119,5 +128,10 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
                          "filter_length / hop_length / win_length do not give one frame per hop")
     mel_total, mel_per_utt = _l1(y_mel, y_hat_mel, float(hps.train.c_mel))
     kl_total, kl_per_utt = _kl(z_p, logs_q, m_p, logs_p, z_mask, float(hps.train.c_kl))
-    return dict(loss_mel=mel_total[1], loss_kl=kl_total[1], mel=mel_total[0], kl=kl_total[0], mel_per_utt=mel_per_utt,
-                kl_per_utt=kl_per_utt, y_hat=o, ids_slice=ids_slice, y_mel=y_mel, y_hat_mel=y_hat_mel)
+    out = dict(loss_mel=mel_total[1], loss_kl=kl_total[1], mel=mel_total[0], kl=kl_total[0], mel_per_utt=mel_per_utt,
+               kl_per_utt=kl_per_utt, y_hat=o, ids_slice=ids_slice, y_mel=y_mel, y_hat_mel=y_hat_mel)
+    if with_duration:
+        c_dur = float(hps.train.c_dur) if "c_dur" in hps.train.keys() else 1.0
+        dur = net_g._duration_from_recon(e_q, eps_w, c_dur)
+        out.update(loss_dur=dur["total"][1], dur=dur["total"][0], dur_per_utt=dur["per_utt"])
+    return out

@@ -90,6 +90,8 @@ class SynthesizerTrn:
         self._blob = None      # CPU float32 blob (weights live here until .to(device))
         self._post_blob = None  # CPU float32 blob of enc_q.* (voice conversion), when the checkpoint carries it
         self._post_on_device = False  # uploaded by the first voice_conversion() call (wetts_load_posterior_encoder)
+        self._dur_blob = None  # CPU float32 blob of dp.flows.1.* / dp.post_* (duration_loss), when the checkpoint has them
+        self._dur_on_device = False  # uploaded by the first duration_loss() call (wetts_load_duration_posterior)
         self._handle = None    # wetts_model_t*
         self._ws = _Workspace()
         self._ws_dec = _Workspace()  # the decoder's own scratch in overlap mode (see set_overlap)
@@ -222,6 +224,9 @@ class SynthesizerTrn:
         self._post_blob = None
         if checkpoint.has_posterior(self.cfg, self.spec_channels, state_dict):
             self._post_blob = checkpoint.pack_posterior_blob(self.cfg, self.spec_channels, state_dict)
+        self._dur_blob = None  # the SDP's forward-only tensors, kept the same way for duration_loss()
+        if checkpoint.has_duration(self.cfg, state_dict):
+            self._dur_blob = checkpoint.pack_duration_blob(self.cfg, state_dict)
         self._destroy()
         if self.device.type == "cuda":
             self._create()
@@ -255,6 +260,10 @@ class SynthesizerTrn:
             pb = self._post_blob.to(blob.device)
             for name, off, numel, shape in checkpoint.posterior_layout(self.cfg, self.spec_channels):
                 sd[name] = pb[off:off + numel].view(shape)
+        if self._dur_blob is not None:  # dp.flows.1.* / dp.post_*, only when the loaded checkpoint carried them
+            db = self._dur_blob.to(blob.device)
+            for name, off, numel, shape in checkpoint.duration_layout(self.cfg):
+                sd[name] = db[off:off + numel].view(shape)
         return sd
 
     def load_blob(self, blob):
@@ -297,6 +306,7 @@ class SynthesizerTrn:
             _lib.load().wetts_destroy(self._handle)
             self._handle = None
         self._post_on_device = False
+        self._dur_on_device = False
 
     def __del__(self):
         try:
@@ -577,6 +587,169 @@ class SynthesizerTrn:
         self._last_recon = dict(st, u=u, ids_slice=ids, z_slice=z_slice, o=o, segment_size=seg)
         return (o, ids, st["attn"].unsqueeze(1), st["x_mask"].unsqueeze(1), st["y_mask"].unsqueeze(1),
                 (st["z"], st["z_p"], st["m_p"], st["logs_p"], st["m_q"], st["logs_q"]))
+
+    # ---- duration loss (models.py:196-206) ---------------------------------------------------------------------------
+    def _require_duration(self):
+        """The SDP's forward-only tensors on the device: uploaded on first use, like the posterior encoder.  A
+        DurationPredictor model needs none."""
+        lib = self._require()
+        if not self.use_sdp:
+            return lib
+        if self._dur_blob is None:
+            names = [n for n, _, _, _ in checkpoint.duration_layout(self.cfg)]
+            raise _lib.WettsError("duration_loss needs the stochastic duration predictor's forward-only tensors, but the "
+                                  f"loaded checkpoint does not carry all of them: {names[0]} ... {names[-1]} "
+                                  "(dp.flows.1.*, dp.post_pre, dp.post_proj, dp.post_convs.*, dp.post_flows.*)")
+        if not self._dur_on_device:
+            with torch.cuda.device(self.device):
+                dev = self._dur_blob.to(self.device)
+                _lib.check(lib.wetts_load_duration_posterior(self._handle, _lib.ptr(dev), dev.numel(),
+                                                             _lib.current_stream_ptr()), "load_duration_posterior")
+            self._dur_on_device = True
+        return lib
+
+    def duration_loss(self, x, x_lengths, w, sid=None, e_q=None, eps_w=None):
+        """How plausible the durations `w` are for the transcript `x` under the checkpoint's duration predictor:
+        forward()'s `l_length` (models.py:196-206) without gradients.  x [B,Tx] phoneme ids, x_lengths [B], w [B,1,Tx]
+        or [B,Tx] frame counts per phoneme -- what align() returns as `w`.  Returns (l_length [B], (x_enc [B,H,Tx],
+        logw [B,1,Tx], logw_ [B,1,Tx])): forward()'s second and eighth elements.
+
+        SDP models: l_length = dp(x, x_mask, w, g) / sum(x_mask), the variational bound nll + logq of
+        duration_predictors.py:206-253 per utterance over the WHOLE batch's phoneme count, logw the predictor's own
+        sample at noise_scale 1.0, logw_ = log(w + 1e-6) * x_mask.  DurationPredictor models: logw = dp(x, x_mask, g),
+        l_length = sum((logw - logw_)^2) / sum(x_mask).  train.py:485 sums l_length into loss_dur; the per-utterance
+        values that do not depend on the batch are kept in `_last_duration` (nll, logq, per_utt).
+
+        Stages on the caller's stream: emb_g -> text encoder -> the SDP forward (or DP and its squared error) -> for
+        SDP models the reverse pass for logw -> the totals.  One host read-back (the status word, at the end).  `e_q`
+        and `eps_w` [B,2,Tx] (optional, not in the reference) inject the torch.randn draws of :229 and :257; without
+        them they come from the Philox kernel under torch.manual_seed, e_q first.
+
+        Shape errors raise ValueError before anything is launched; a negative or non-finite w under the mask raises
+        ValueError after the read-back; ids outside their tables raise IndexError.  An utterance of length 0 divides
+        0 by 0: its `_last_duration["per_utt"]` is NaN (and every l_length, if no utterance has a phoneme).  An SDP checkpoint without the
+        forward-only tensors (dp.flows.1.*, dp.post_*) raises a RuntimeError naming them."""
+        x = torch.as_tensor(x)
+        if x.dim() != 2:
+            raise ValueError(f"x must be [B, Tx], got {tuple(x.shape)}")
+        B, Tx = x.shape
+        if tuple(torch.as_tensor(x_lengths).shape) != (B,):
+            raise ValueError(f"x_lengths must be [{B}], got {tuple(torch.as_tensor(x_lengths).shape)}")
+        w = torch.as_tensor(w)
+        if tuple(w.shape) not in ((B, 1, Tx), (B, Tx)):
+            raise ValueError(f"w must be [{B},1,{Tx}] or [{B},{Tx}], got {tuple(w.shape)}")
+        if self.n_speakers > 0 and sid is None:
+            raise ValueError("sid is required when n_speakers > 0")
+        for name, t in (("e_q", e_q), ("eps_w", eps_w)):
+            if t is not None and tuple(t.shape) != (B, 2, Tx):
+                raise ValueError(f"{name} must be [{B},2,{Tx}], got {tuple(t.shape)}")
+        if B < 1 or Tx < 1:
+            raise ValueError("duration_loss of an empty batch")
+        lib = self._require_duration()
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        H, I = self.hidden_channels, self.inter_channels
+        x, x_lengths = self._ids(x), self._ids(x_lengths)
+        nws = int(lib.wetts_workspace_bytes(self._handle, B, Tx, 0))
+        ws = (self._ws_dec if self.overlap else self._ws).get(nws, dev)
+        s = _lib.current_stream_ptr()
+        g_buf = torch.empty(B, max(1, self.gin_channels), **f32)
+        g = g_buf if self.n_speakers > 0 else None
+        x_enc, stats, x_mask = torch.empty(B, H, Tx, **f32), torch.empty(B, 2 * I, Tx, **f32), torch.empty(B, Tx, **f32)
+        status = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.wetts_set_status_word(self._handle, _lib.ptr(status), s), "set_status_word")
+        try:
+            _lib.check(lib.wetts_speaker_embedding(self._handle, _lib.ptr(self._ids(sid)) if g is not None else None, B,
+                                                   _lib.ptr(g_buf), s), "speaker_embedding")
+            _lib.check(lib.wetts_text_encoder(self._handle, _lib.ptr(x), _lib.ptr(x_lengths), _lib.ptr(g), B, Tx,
+                                              _lib.ptr(x_enc), _lib.ptr(stats), _lib.ptr(x_mask), _lib.ptr(ws), nws, s),
+                       "text_encoder")
+            st = self._duration_stages(lib, x_enc, x_mask, g, w, e_q, eps_w, status, 1.0)
+        finally:
+            lib.wetts_set_status_word(self._handle, None, s)
+        self.last_status = int(status.cpu().item()) & 0xFFFFFFFF  # the call's one host sync
+        self._duration_raise()
+        self._last_duration = st
+        return st["l_length"], (x_enc, st["logw"].unsqueeze(1), st["logw_"].unsqueeze(1))
+
+    def _duration_stages(self, lib, x_enc, x_mask, g, w, e_q, eps_w, status, weight):
+        """The launches of duration_loss() behind the text encoder on device tensors x_enc [B,H,Tx], x_mask [B,Tx], g
+        [B,gin] or None, without the read-back -> stage dict.  `status` is the registered status word.  Shared with
+        losses.teacher_forced_losses(with_duration=True), which feeds reconstruct()'s tensors."""
+        B, H, Tx = x_enc.shape
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        s = _lib.current_stream_ptr()
+        w = self._f32(torch.as_tensor(w)).reshape(B, Tx)
+        logw, logw_ = torch.empty(B, Tx, **f32), torch.empty(B, Tx, **f32)
+        rows, per_utt, l_length = (torch.empty(B, **f32) for _ in range(3))
+        total = torch.empty(2, **f32)
+        nws = max(int(lib.wetts_workspace_bytes(self._handle, B, Tx, 0)),
+                  int(lib.wetts_duration_loss_workspace_bytes(self._handle, B, Tx)))
+        ws = (self._ws_dec if self.overlap else self._ws).get(nws, dev)
+        st = dict(x_mask=x_mask, w=w, nll=None, logq=None, e_q=None, eps_w=None)
+        if self.use_sdp:
+            e_q = self._randn(B, 2, Tx) if e_q is None else self._f32(e_q)
+            eps_w = self._randn(B, 2, Tx) if eps_w is None else self._f32(eps_w)
+            nll, logq = torch.empty(B, **f32), torch.empty(B, **f32)
+            z_q, z = torch.empty(B, 2, Tx, **f32), torch.empty(B, 2, Tx, **f32)
+            nll_terms, logq_terms = torch.empty(B, Tx, **f32), torch.empty(B, Tx, **f32)
+            _lib.check(lib.wetts_duration_sdp_forward(self._handle, _lib.ptr(x_enc), _lib.ptr(x_mask), _lib.ptr(g),
+                                                      _lib.ptr(w), _lib.ptr(e_q), B, Tx, _lib.ptr(nll), _lib.ptr(logq),
+                                                      _lib.ptr(rows), _lib.ptr(per_utt), _lib.ptr(z_q), _lib.ptr(z), _lib.ptr(nll_terms),
+                                                      _lib.ptr(logq_terms), _lib.ptr(status), _lib.ptr(ws), nws, s),
+                       "duration_sdp_forward")
+            # models.py:200: logw = dp(x, x_mask, g=g, reverse=True, noise_scale=1.0)
+            _lib.check(lib.wetts_duration_sdp(self._handle, _lib.ptr(x_enc), _lib.ptr(x_mask), _lib.ptr(g),
+                                              _lib.ptr(eps_w), 1.0, B, Tx, _lib.ptr(logw), _lib.ptr(status), _lib.ptr(ws),
+                                              nws, s), "duration_sdp")
+            # logw_ = log(w + 1e-6) * x_mask (models.py:201)
+            _lib.check(lib.wetts_duration_logw_target(_lib.ptr(w), _lib.ptr(x_mask), B, Tx, _lib.ptr(logw_), s),
+                       "duration_logw_target")
+            st.update(nll=nll, logq=logq, z_q=z_q, z=z, nll_terms=nll_terms, logq_terms=logq_terms, e_q=e_q, eps_w=eps_w)
+        else:
+            _lib.check(lib.wetts_duration_dp(self._handle, _lib.ptr(x_enc), _lib.ptr(x_mask), _lib.ptr(g), B, Tx,
+                                             _lib.ptr(logw), _lib.ptr(ws), nws, s), "duration_dp")
+            _lib.check(lib.wetts_duration_dp_loss(self._handle, _lib.ptr(logw), _lib.ptr(w), _lib.ptr(x_mask), B, Tx,
+                                                  _lib.ptr(logw_), _lib.ptr(rows), _lib.ptr(per_utt), s),
+                       "duration_dp_loss")
+        _lib.check(lib.wetts_duration_loss_total(_lib.ptr(rows), _lib.ptr(x_mask), B, Tx, float(weight),
+                                                 _lib.ptr(l_length), _lib.ptr(total), s), "duration_loss_total")
+        st.update(rows=rows, per_utt=per_utt, l_length=l_length, total=total, logw=logw, logw_=logw_)
+        return st
+
+    def _duration_from_recon(self, e_q, eps_w, weight):
+        """The duration stages on what the last reconstruct() computed (losses.teacher_forced_losses)."""
+        lib = self._require_duration()
+        rc = self._last_recon
+        B, _, Tx = rc["x_enc"].shape
+        for name, t in (("e_q", e_q), ("eps_w", eps_w)):
+            if t is not None and tuple(t.shape) != (B, 2, Tx):
+                raise ValueError(f"{name} must be [{B},2,{Tx}], got {tuple(t.shape)}")
+        s = _lib.current_stream_ptr()
+        status = torch.empty(1, dtype=torch.int64, device=self.device)
+        _lib.check(lib.wetts_set_status_word(self._handle, _lib.ptr(status), s), "set_status_word")
+        try:
+            st = self._duration_stages(lib, rc["x_enc"], rc["x_mask"], rc["g"], rc["w"], e_q, eps_w, status, weight)
+        finally:
+            lib.wetts_set_status_word(self._handle, None, s)
+        self.last_status = int(status.cpu().item()) & 0xFFFFFFFF
+        self._duration_raise()
+        self._last_duration = st
+        return st
+
+    def _duration_raise(self):
+        """What duration_loss() raises from the status word it read back (self.last_status)."""
+        if self.last_status & _lib.STATUS_PHONE_ID_RANGE:
+            raise IndexError("index out of range in self (phoneme id outside emb, encoders.py:48)")
+        if self.last_status & _lib.STATUS_SPEAKER_ID_RANGE:
+            raise IndexError("index out of range in self (sid outside emb_g, models.py:163)")
+        if self.last_status & _lib.STATUS_DURATION_NEGATIVE:
+            raise ValueError("duration_loss: w holds a negative duration")
+        if self.last_status & _lib.STATUS_DURATION_NONFINITE:
+            raise ValueError("duration_loss: w holds a NaN or infinite duration")
+        if self.last_status & _lib.STATUS_SPLINE_DOMAIN:
+            raise AssertionError("spline inverse: negative discriminant (transforms.py:171)")
 
     # ---- stages ----------------------------------------------------------------------------------
     def _ids(self, t):

@@ -139,6 +139,27 @@ def make_posterior_state_dict(cfg, spec_channels, seed=0):
     return sd
 
 
+def make_duration_state_dict(cfg, seed=0):
+    """Reference-keyed tensors of the duration posterior's blob (checkpoint.duration_layout: `dp.flows.1.*`,
+    `dp.post_*`; StochasticDurationPredictor, duration_predictors.py:176-195) for `cfg`, deterministic in `seed`, from a
+    generator of their own (make_state_dict's stream, and so every stored blob checksum, is untouched).  Values as
+    make_state_dict gives the main ConvFlows: the `proj` the reference zero-initialises is non-zero, so no spline is
+    the identity.  Empty for a DurationPredictor model."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    for name, _, _, shape in checkpoint.duration_layout(cfg):
+        w = torch.randn(*shape, generator=g, dtype=torch.float32)
+        if name.endswith(".gamma"):
+            sd[name] = 1.0 + 0.1 * w
+        elif name.endswith(".beta") or name.endswith(".bias"):
+            sd[name] = 0.05 * w
+        elif name.endswith(".m") or name.endswith(".logs"):  # post_flows.0: ElementwiseAffine
+            sd[name] = 0.1 * w
+        else:
+            sd[name] = w * _std_for(name, shape, cfg)
+    return sd
+
+
 def blob_checksum(blob):
     """Order-sensitive fingerprint of a float32 blob (guards golden fixtures against RNG drift)."""
     b = blob.detach().to(torch.float64)
