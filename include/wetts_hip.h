@@ -610,6 +610,61 @@ int32_t wetts_profile_hifigan(const wetts_model_t* m, const float* z, int64_t z_
                               float* audio, void* workspace, int64_t workspace_bytes, void* stream,
                               double* mrf_ms, double* total_ms, int32_t* mrf_launches);
 
+/* ---- MultiPeriodDiscriminator and the adversarial losses (csrc/discriminator.hip) ------------------------------
+ *
+ * model/discriminators.py:21-124,228-254 with use_spectral_norm = false, without gradients: DiscriminatorS and
+ * DiscriminatorP for the periods 2, 3, 5, 7, 11, and losses.py:6-42.  The architecture has no configuration, so the
+ * blob layout is fixed: the 74 tensors `discriminators.N.convs.M.{weight,bias}` / `discriminators.N.conv_post.*` with
+ * weight norm folded, Conv2d weights in their [Cout, Cin, k, 1] shape.  A handle of its own: wetts_model_t and its
+ * three blobs know nothing of it. */
+typedef struct wetts_disc wetts_disc_t;
+
+int32_t wetts_disc_blob_num_tensors(void);
+int32_t wetts_disc_blob_tensor_info(int32_t index, char* name_buf, size_t name_buf_len, int64_t* offset,
+                                    int64_t* numel, int64_t shape[4]);
+int64_t wetts_disc_blob_numel(void);
+/* Copies the device blob (a set-up call like the model's create: allocates, returns after `stream` has drained). */
+int32_t wetts_disc_create(const float* blob_dev, int64_t blob_numel, void* stream, wetts_disc_t** out);
+void wetts_disc_destroy(wetts_disc_t* d);
+
+/* Internal shape {rows, C, H, p} of feature map `index` (0..6: DiscriminatorS's seven layers, then six per period) for
+ * B utterance PAIRS of T samples: rows = 2B * p.  A period stack's map is the contiguous [2B][p][C][H], whose
+ * permutation (0, 2, 3, 1) is the reference's [2B, C, H, p]; its conv_post map is stored as the
+ * reference has it, [2B][1][H][p]; DiscriminatorS's maps (p = 1) are the reference's [2B][C][T'].  The first B
+ * utterances are the real ones. */
+int32_t wetts_disc_fmap_shape(int32_t B, int32_t T, int32_t index, int64_t shape[4]);
+
+/* All six stacks on y and y_hat [B, 1, T] as one batch of 2B.  fmaps_host: 37 device buffers of the shapes above, owned
+ * by the caller; every layer's output is one of them, so the call needs no workspace.  T >= 6, the shortest length at
+ * which every reflect pad of discriminators.py:81-84 is legal (n_pad < T for each period). */
+int32_t wetts_disc_forward(const wetts_disc_t* d, const float* y, const float* y_hat, int32_t B, int32_t T,
+                           float* const* fmaps_host, void* stream);
+
+/* One layer of one stack on `rows` independent rows, with the kernels and weights the forward pass uses: the reflect
+ * pad + fold + conv 0 of period stack `disc` (1..5) on rows utterances [rows, T] -> [rows * p][32][H1]; an MFMA conv
+ * (layers 1..4 of a period stack, layer 5 of DiscriminatorS) on x [rows][Cin][Hin]; conv_post on `rows` utterances
+ * ([rows * p][1024][H] in); a grouped conv of DiscriminatorS (layers 0..4) on x [rows][Cin][Tin]. */
+int32_t wetts_disc_fold_conv0(const wetts_disc_t* d, int32_t disc, const float* y, int32_t rows, int32_t T, float* out,
+                              void* stream);
+int32_t wetts_disc_strided_conv(const wetts_disc_t* d, int32_t disc, int32_t layer, const float* x, int64_t rows,
+                                int32_t Hin, float* out, void* stream);
+int32_t wetts_disc_conv_post(const wetts_disc_t* d, int32_t disc, const float* x, int32_t rows, int32_t H, float* out,
+                             void* stream);
+int32_t wetts_disc_grouped_conv(const wetts_disc_t* d, int32_t layer, const float* x, int32_t rows, int32_t Tin,
+                                float* out, void* stream);
+
+/* losses.py:6-42 over n (real, generated) tensor pairs; utterance b of pair i owns the N_host[i] contiguous floats at
+ * a_host[i] + b * a_bs_host[i] (g likewise).  kind 0, feature_loss: item_a[i] = mean |a - g|, scale 2.  kind 1,
+ * discriminator_loss: item_a[i] = mean (1 - a)^2, item_g[i] = mean g^2.  kind 2, generator_loss: item_a[i] =
+ * mean (1 - a)^2 (g unused).  total[0] = scale * the sum over items, per_utt[b] the same from utterance b's own
+ * elements; sums: 2 * n * B float64 of scratch (the sums are carried in float64, in a fixed order, and round to f32 at
+ * the store).  No atomics: results repeat bit for bit and
+ * per_utt[b] does not depend on the batch. */
+int32_t wetts_disc_losses(int32_t kind, int32_t n, const float* const* a_host, const float* const* g_host,
+                          const int64_t* a_bs_host, const int64_t* g_bs_host, const int64_t* N_host, int32_t B,
+                          float scale, double* sums, float* item_a, float* item_g, float* per_utt, float* total,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

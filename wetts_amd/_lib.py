@@ -156,6 +156,20 @@ SIGNATURES = {
     "wetts_profile_hifigan": (_I32, [_P, _P, _I64, _I64, _P, _I32, _I32, _P, _P, _I64, _P,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(_I32)]),
+    "wetts_disc_blob_num_tensors": (_I32, []),
+    "wetts_disc_blob_tensor_info": (_I32, [_I32, C.c_char_p, C.c_size_t, C.POINTER(_I64), C.POINTER(_I64),
+                                           C.POINTER(_I64 * 4)]),
+    "wetts_disc_blob_numel": (_I64, []),
+    "wetts_disc_create": (_I32, [_P, _I64, _P, C.POINTER(_P)]),
+    "wetts_disc_destroy": (None, [_P]),
+    "wetts_disc_fmap_shape": (_I32, [_I32, _I32, _I32, C.POINTER(_I64 * 4)]),
+    "wetts_disc_forward": (_I32, [_P, _P, _P, _I32, _I32, C.POINTER(_P), _P]),
+    "wetts_disc_fold_conv0": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
+    "wetts_disc_strided_conv": (_I32, [_P, _I32, _I32, _P, _I64, _I32, _P, _P]),
+    "wetts_disc_conv_post": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
+    "wetts_disc_grouped_conv": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
+    "wetts_disc_losses": (_I32, [_I32, _I32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64),
+                                 C.POINTER(_I64), _I32, _F, _P, _P, _P, _P, _P, _P]),
 }
 
 # WETTS_STATUS_* bits of include/wetts_hip.h

@@ -202,6 +202,47 @@ def pack_duration_blob(cfg, state_dict):
     return blob
 
 
+def disc_layout():
+    """[(name, offset, numel, shape)] of the MultiPeriodDiscriminator's blob (`discriminators.N.convs.M.*`,
+    `discriminators.N.conv_post.*`, weight norm folded), as the library defines it (wetts_disc_blob_tensor_info).  The
+    architecture has no configuration, so neither has the layout."""
+    lib = _lib.load()
+    out = []
+    buf = C.create_string_buffer(256)
+    off, num, shape = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+    for i in range(lib.wetts_disc_blob_num_tensors()):
+        _lib.check(lib.wetts_disc_blob_tensor_info(i, buf, 256, C.byref(off), C.byref(num), C.byref(shape)),
+                   "disc_blob_tensor_info")
+        shp = tuple(int(s) for s in shape if s > 0)
+        out.append((buf.value.decode(), int(off.value), int(num.value), shp))
+    return out
+
+
+def disc_numel():
+    return int(_lib.load().wetts_disc_blob_numel())
+
+
+def pack_disc_blob(state_dict):
+    """Natural-layout float32 CPU blob of the discriminator from a reference-keyed state_dict (a `D_*.pth`'s "model"):
+    weight-norm pairs in either spelling are folded (Conv2d weights [Cout, Cin, k, 1]: the norm runs over all dims but
+    0).  Every tensor must be present and have its layout shape."""
+    sd = fold_weight_norm(state_dict)
+    blob = torch.zeros(disc_numel(), dtype=torch.float32)
+    missing = []
+    for name, off, numel, shape in disc_layout():
+        t = sd.get(name)
+        if t is None:
+            missing.append(name)
+            continue
+        t = t.detach().to(torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != expected {shape}")
+        blob[off:off + numel] = t.reshape(-1)
+    if missing:
+        raise KeyError(f"{len(missing)} discriminator tensors missing from checkpoint: {missing}")
+    return blob
+
+
 def load_state_dict_file(checkpoint_path):
     """Reads `G_*.pth` as saved by task.save_checkpoint (task.py:59-76): {"model": state_dict,
     "iteration", "optimizer", "learning_rate"}; a bare state_dict is accepted too."""

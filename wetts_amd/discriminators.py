@@ -1,0 +1,173 @@
+"""MultiPeriodDiscriminator (model/discriminators.py:228-254: one DiscriminatorS and DiscriminatorP for the periods 2, 3,
+5, 7, 11, all weight-normed) as a drop-in evaluation module on the device.  No gradients.  torch allocates the feature
+maps and takes views; the arithmetic is the HIP kernels of csrc/discriminator.hip.
+
+y and y_hat run as one batch of 2B utterances, so every weight is read once; the results do not depend on the pairing
+(an utterance's maps are a function of that utterance alone, bit for bit).  A period stack's feature map is computed as
+[2B, p, C, H] and handed back as the permuted view [2B, C, H, p] -- the reference's shape, no copy -- split into its real
+and generated halves."""
+import ctypes as C
+
+import torch
+
+from . import _lib, checkpoint
+
+PERIODS = (2, 3, 5, 7, 11)
+N_FMAPS = 37  # DiscriminatorS: 6 convs + conv_post; each DiscriminatorP: 5 convs + conv_post
+# F.pad(x, (0, n_pad), "reflect") needs n_pad < T.  n_pad = p - T % p for the periods that do not divide T: at T = 5,
+# period 11 would pad 6 samples (illegal); from T = 6 on every pad is shorter than the input (checked for every T up to
+# 11 * 11 in tests/test_cpu_disc.py; beyond that n_pad <= 10 < T).
+MIN_SAMPLES = 6
+
+
+class MultiPeriodDiscriminator:
+    def __init__(self, use_spectral_norm=False):
+        if use_spectral_norm:
+            raise NotImplementedError("use_spectral_norm=True is not supported: folding spectral norm needs the "
+                                      "power-iteration state (weight_u / weight_v); no checked-in recipe sets it")
+        self.use_spectral_norm = False
+        self.periods = PERIODS
+        self.training = False
+        self._blob = None      # folded float32 CPU blob (checkpoint.disc_layout order)
+        self._handle = None
+        self._device = None
+        self._shapes = {}      # (B, T) -> [(rows, C, H, p)] * 37
+
+    # ---- nn.Module-like surface ----
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("this discriminator is evaluation only (no gradients)")
+        return self
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Reference-keyed state_dict (`discriminators.N.convs.M.{bias,weight_g,weight_v}`, either weight-norm spelling,
+        or already folded `weight`s).  Every tensor must be present: there is no init value to fall back to."""
+        self._blob = checkpoint.pack_disc_blob(state_dict)
+        if self._device is not None:
+            self._create()
+        return self
+
+    def state_dict(self):
+        """The folded tensors (weight norm collapsed), reference-keyed."""
+        self._require_blob()
+        return {name: self._blob[off:off + numel].reshape(shape).clone()
+                for name, off, numel, shape in checkpoint.disc_layout()}
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("MultiPeriodDiscriminator runs on a HIP device only (there is no CPU path)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self._device = device
+        if self._blob is not None:
+            self._create()
+        return self
+
+    def cuda(self, device=None):
+        return self.to("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+
+    def _require_blob(self):
+        if self._blob is None:
+            raise RuntimeError("no weights: call load_state_dict() (or models.load_checkpoint on a D_*.pth) first")
+
+    def _create(self):
+        self._destroy()
+        lib = _lib.load()
+        with torch.cuda.device(self._device):
+            dev = self._blob.to(self._device)
+            h = C.c_void_p()
+            _lib.check(lib.wetts_disc_create(_lib.ptr(dev), dev.numel(), _lib.current_stream_ptr(), C.byref(h)),
+                       "disc_create")
+        self._handle = h
+
+    def _destroy(self):
+        if self._handle is not None:
+            _lib.load().wetts_disc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    def _require(self):
+        self._require_blob()
+        if self._handle is None:
+            raise RuntimeError("the discriminator is not on a device: call .to('cuda') / .cuda() first")
+
+    # ---- forward ----
+    @staticmethod
+    def fmap_shapes(B, T):
+        """[(rows, C, H, p)] of the 37 feature maps as the device computes them (wetts_disc_fmap_shape)."""
+        lib = _lib.load()
+        out, shp = [], (C.c_int64 * 4)()
+        for i in range(N_FMAPS):
+            _lib.check(lib.wetts_disc_fmap_shape(int(B), int(T), i, C.byref(shp)), "disc_fmap_shape")
+            out.append(tuple(int(v) for v in shp))
+        return out
+
+    def _check(self, y, y_hat):
+        for t, n in ((y, "y"), (y_hat, "y_hat")):
+            if not torch.is_tensor(t) or t.dim() != 3 or t.shape[1] != 1:
+                raise ValueError(f"{n} must be a [B, 1, T] tensor, got {getattr(t, 'shape', type(t))}")
+            if t.device.type != "cuda":
+                raise ValueError(f"{n} must be on a HIP device (there is no CPU path)")
+        if tuple(y.shape) != tuple(y_hat.shape):
+            raise ValueError(f"y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} must have one shape")
+        if y.shape[0] < 1:
+            raise ValueError("empty batch")
+        if y.shape[2] < MIN_SAMPLES:
+            raise ValueError(f"T = {y.shape[2]} samples: the reflect pad of discriminators.py:81-84 needs at least "
+                             f"{MIN_SAMPLES}")
+        self._require()
+        if y.device != self._device or y_hat.device != self._device:
+            raise ValueError(f"y is on {y.device}, y_hat on {y_hat.device}, the discriminator on {self._device}")
+
+    def _run(self, y, y_hat):
+        """-> (buffers [37] as the device wrote them, B): S maps [2B, C, T'], P maps [2B, p, C, H], P conv_post maps
+        [2B, 1, H, p]; all slices of one torch-owned allocation made for this call."""
+        self._check(y, y_hat)
+        y = y.to(torch.float32).contiguous()
+        y_hat = y_hat.to(torch.float32).contiguous()
+        B, _, T = y.shape
+        shapes = self._shapes.get((B, T))
+        if shapes is None:
+            shapes = self._shapes[(B, T)] = self.fmap_shapes(B, T)
+        offs, total = [], 0
+        for rows, Cc, H, p in shapes:
+            offs.append(total)
+            total += (rows * Cc * H + 63) // 64 * 64
+        flat = torch.empty(total, dtype=torch.float32, device=y.device)
+        bufs = []
+        for i, ((rows, Cc, H, p), off) in enumerate(zip(shapes, offs)):
+            t = flat[off:off + rows * Cc * H]
+            post = i >= 7 and (i - 7) % 6 == 5
+            bufs.append(t.view(2 * B, 1, H, p) if post else (t.view(2 * B, p, Cc, H) if i >= 7 else t.view(2 * B, Cc, H)))
+        ptrs = (C.c_void_p * N_FMAPS)(*[b.data_ptr() for b in bufs])
+        with torch.cuda.device(y.device):
+            _lib.check(_lib.load().wetts_disc_forward(self._handle, _lib.ptr(y), _lib.ptr(y_hat), B, T, ptrs,
+                                                      _lib.current_stream_ptr()), "disc_forward")
+        return bufs, B
+
+    def forward(self, y, y_hat):
+        """discriminators.py:241-254 -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs): six [B, N_d] outputs each, and six lists of
+        feature maps in the reference's shapes ([B, C, T'] for DiscriminatorS, [B, C, H, p] for the period stacks)."""
+        bufs, B = self._run(y, y_hat)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        i = 0
+        for d in range(6):
+            n = 7 if d == 0 else 6
+            maps = [b if (d == 0 or k == n - 1) else b.permute(0, 2, 3, 1) for k, b in enumerate(bufs[i:i + n])]
+            i += n
+            fmap_rs.append([m[:B] for m in maps])
+            fmap_gs.append([m[B:] for m in maps])
+            y_d_rs.append(maps[-1][:B].reshape(B, -1))
+            y_d_gs.append(maps[-1][B:].reshape(B, -1))
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+    __call__ = forward

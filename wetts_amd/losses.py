@@ -1,6 +1,6 @@
-"""The generator-side losses of the reference's training loop that need no discriminator (losses.kl_loss,
-losses.py:45-60, the mel L1 of train.py:486 and the duration loss of train.py:485) as evaluation metrics on the device,
-and `teacher_forced_losses`, which does for one batch what train.py:400-432,485-488 does with
+"""The losses of the reference's training loop -- losses.kl_loss (losses.py:45-60), the mel L1 of train.py:486, the
+duration loss of train.py:485, and the adversarial terms discriminator_loss / generator_loss / feature_loss
+(losses.py:6-42, csrc/discriminator.hip) -- as evaluation metrics on the device, and `teacher_forced_losses`, which does for one batch what train.py:400-432,485-488 does with
 SynthesizerTrn.reconstruct() and SynthesizerTrn.duration_loss()'s stages in the place of forward().  No gradients; torch
 allocates and takes views, the arithmetic is the HIP kernels of csrc/losses.hip and csrc/duration_loss.hip.
 
@@ -10,6 +10,8 @@ finding the bad transcript or the clipped recording in a corpus.  The duration l
 stochastic duration predictor's nll + logq, or the DurationPredictor's squared error) divides by the whole batch's
 phoneme count as the reference does; `dur_per_utt` is each utterance's own sum over its own phoneme count.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib, commons
@@ -85,12 +87,93 @@ def _l1(a, b, weight):
     return total, per_utt
 
 
+def _rows(t, like=None):
+    """-> (tensor kept alive, batch stride, N): utterance b of `t` [B, ...] owns N contiguous floats at
+    data_ptr + b * stride.  A permuted view whose utterances are contiguous blocks (the period stacks' feature maps) is
+    taken as it lies -- a sum over an utterance does not care in which order the block is laid out, as long as real and
+    generated agree (`like`: the partner's strides); anything else is copied."""
+    B = t.shape[0]
+    N = t.numel() // B
+    if t.dtype == torch.float32 and (like is None or like == t.stride()):
+        order = sorted(range(1, t.dim()), key=lambda i: -t.stride(i))
+        if t.permute(0, *order).is_contiguous():
+            return t, N, N
+    return t.to(torch.float32).contiguous(), N, N
+
+
+def _disc_reduce(kind, reals, gens, scale, what):
+    """wetts_disc_losses over the tensor pairs -> (total [1], item_a [n], item_g [n], per_utt [B])."""
+    reals = list(reals)
+    gens = list(gens) if gens is not None else None
+    n = len(reals)
+    if n < 1 or n > 40 or (gens is not None and len(gens) != n):
+        raise ValueError(f"{what}: needs 1 .. 40 tensors (and as many generated as real), got {n}")
+    dev, B = None, None
+    a, g = [], []
+    for i in range(n):
+        pair = (reals[i],) if gens is None else (reals[i], gens[i])
+        for t in pair:
+            if not torch.is_tensor(t) or t.dim() < 1 or t.numel() < 1:
+                raise ValueError(f"{what}: item {i} must be a non-empty tensor whose first dimension is the batch")
+            if t.device.type != "cuda":
+                raise ValueError(f"{what}: item {i} must be on a HIP device (there is no CPU path)")
+            dev, B = (t.device, t.shape[0]) if dev is None else (dev, B)
+            if t.device != dev or t.shape[0] != B:
+                raise ValueError(f"{what}: item {i} is [{t.shape[0]}, ...] on {t.device}, expected [{B}, ...] on {dev}")
+        if gens is not None and tuple(pair[0].shape) != tuple(pair[1].shape):
+            raise ValueError(f"{what}: item {i}: {tuple(pair[0].shape)} against {tuple(pair[1].shape)}")
+        same = gens is None or pair[0].stride() == pair[1].stride()
+        a.append(_rows(pair[0]) if same else _rows(pair[0].contiguous()))
+        if gens is not None:
+            g.append(_rows(pair[1], a[-1][0].stride()))
+    P, I64 = C.c_void_p * n, C.c_int64 * n
+    sums = torch.empty(2 * n * B, dtype=torch.float64, device=dev)
+    item_a = torch.empty(n, dtype=torch.float32, device=dev)
+    item_g = torch.empty(n, dtype=torch.float32, device=dev)
+    per_utt = torch.empty(B, dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().wetts_disc_losses(
+            kind, n, P(*[t.data_ptr() for t, _, _ in a]), P(*[t.data_ptr() for t, _, _ in g]) if g else None,
+            I64(*[s for _, s, _ in a]), I64(*[s for _, s, _ in g]) if g else None, I64(*[N for _, _, N in a]), B,
+            float(scale), _lib.ptr(sums), _lib.ptr(item_a), _lib.ptr(item_g), _lib.ptr(per_utt), _lib.ptr(total),
+            _lib.current_stream_ptr()), what)
+    return total, item_a, item_g, per_utt
+
+
+def feature_loss(fmap_r, fmap_g, *, per_utterance=False):
+    """losses.py:6-14: 2 * sum over every layer of every discriminator of mean |real - generated|.  Returns a 0-d
+    device tensor, or (loss, per_utt [B]) with `per_utterance=True`: the same from each utterance's own elements."""
+    total, _, _, per_utt = _feature(fmap_r, fmap_g)
+    return (total[0], per_utt) if per_utterance else total[0]
+
+
+def _feature(fmap_r, fmap_g):
+    """feature_loss -> (total [1], per-layer mean |r - g| [n], unused, per_utt [B])."""
+    return _disc_reduce(0, [l for d in fmap_r for l in d], [l for d in fmap_g for l in d], 2.0, "feature_loss")
+
+
+def discriminator_loss(disc_real_outputs, disc_generated_outputs, *, per_utterance=False):
+    """losses.py:17-30: sum over the discriminators of mean (1 - dr)^2 + mean dg^2.  Returns (loss, r_losses, g_losses)
+    -- a 0-d device tensor and two device tensors [n] (the reference's lists of floats, without the read-back) --,
+    with `per_utterance=True` also per_utt [B]."""
+    total, r, g, per_utt = _disc_reduce(1, disc_real_outputs, disc_generated_outputs, 1.0, "discriminator_loss")
+    return (total[0], r, g, per_utt) if per_utterance else (total[0], r, g)
+
+
+def generator_loss(disc_outputs, *, per_utterance=False):
+    """losses.py:33-42: sum over the discriminators of mean (1 - dg)^2.  Returns (loss, gen_losses [n]), with
+    `per_utterance=True` also per_utt [B]."""
+    total, gl, _, per_utt = _disc_reduce(2, disc_outputs, None, 1.0, "generator_loss")
+    return (total[0], gl, per_utt) if per_utterance else (total[0], gl)
+
+
 def _flag(section, key):
     return key in section.keys() and bool(section[key])
 
 
 def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None, with_duration=False, e_q=None,
-                          eps_w=None, **reconstruct_kwargs):
+                          eps_w=None, net_d=None, y=None, **reconstruct_kwargs):
     """train.py:400-432,486-488 for one batch, without gradients: net_g.reconstruct(...) in the place of net_g(...), the
     target mel (`spec` itself for a mel posterior encoder, else spec_to_mel_torch(spec)) sliced at ids_slice, the mel
     spectrogram of the decoded slice, and
@@ -107,8 +190,15 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
     predictor's stages of SynthesizerTrn.duration_loss() on reconstruct()'s own w, x_enc, x_mask and g (no second text
     encoder pass; `e_q` / `eps_w` [B,2,Tx] inject its draws), and the entries loss_dur (sum_b l_length[b], weighted by
     hps.train.c_dur where the recipe has one, else 1), dur (unweighted) and dur_per_utt [B].  It costs one more
-    read-back of the status word."""
+    read-back of the status word.
+
+    `net_d` (a MultiPeriodDiscriminator) with `y`, the batch's waveform [B, 1, T_wav], adds the adversarial terms of
+    train.py:431-439,480-491: y is sliced at ids_slice * hop, net_d(y_slice, y_hat) runs once, and the entries are
+    loss_disc, loss_gen, loss_fm (scalars), loss_disc_per_utt, loss_gen_per_utt, loss_fm_per_utt [B], losses_disc_r,
+    losses_disc_g and losses_gen [6], and y_slice [B, 1, segment * hop].  Without `net_d` nothing changes."""
     d = hps.data
+    if (net_d is None) != (y is None):
+        raise ValueError("net_d and y (the batch's waveform [B, 1, T_wav]) go together")
     if int(net_g.hop_length) != int(d.hop_length):
         raise ValueError(f"the model produces {net_g.hop_length} samples per frame but hps.data.hop_length is "
                          f"{d.hop_length}: the mel spectrogram of the decoded slice would not line up with the target")
@@ -134,4 +224,13 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
         c_dur = float(hps.train.c_dur) if "c_dur" in hps.train.keys() else 1.0
         dur = net_g._duration_from_recon(e_q, eps_w, c_dur)
         out.update(loss_dur=dur["total"][1], dur=dur["total"][0], dur_per_utt=dur["per_utt"])
+    if net_d is not None:
+        y_slice = commons.slice_segments(y, ids_slice, seg, scale=int(net_g.hop_length))
+        y_d_r, y_d_g, fmap_r, fmap_g = net_d(y_slice, o)
+        loss_disc, r_losses, g_losses, disc_pu = discriminator_loss(y_d_r, y_d_g, per_utterance=True)
+        loss_gen, gen_losses, gen_pu = generator_loss(y_d_g, per_utterance=True)
+        loss_fm, fm_pu = feature_loss(fmap_r, fmap_g, per_utterance=True)
+        out.update(loss_disc=loss_disc, loss_gen=loss_gen, loss_fm=loss_fm, loss_disc_per_utt=disc_pu,
+                   loss_gen_per_utt=gen_pu, loss_fm_per_utt=fm_pu, losses_disc_r=r_losses, losses_disc_g=g_losses,
+                   losses_gen=gen_losses, y_slice=y_slice)
     return out

@@ -160,6 +160,27 @@ def make_duration_state_dict(cfg, seed=0):
     return sd
 
 
+def make_discriminator_state_dict(seed=0):
+    """Reference-keyed state_dict of MultiPeriodDiscriminator (discriminators.py:228-239) with old-style weight-norm
+    pairs on every conv, as a `D_*.pth` holds them, deterministic in `seed` from a generator of its own.  Weights are
+    randn * sqrt(2 / fan_in) with fan_in = (Cin / groups) * k, biases 0.05 * randn: activations stay O(1) through all
+    seven layers (the reference's default init gives outputs of rms ~ 0.014 that are almost all bias, on which a parity
+    test would test nothing)."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    for name, _, _, shape in checkpoint.disc_layout():
+        base, kind = name.rsplit(".", 1)
+        if kind == "bias":
+            sd[name] = 0.05 * torch.randn(*shape, generator=g, dtype=torch.float32)
+            continue
+        fan_in = shape[1] * shape[2]
+        w = torch.randn(*shape, generator=g, dtype=torch.float32) * math.sqrt(2.0 / fan_in)
+        norm = torch.linalg.vector_norm(w, ord=2, dim=tuple(range(1, w.dim())), keepdim=True)
+        sd[base + ".weight_g"] = norm * (1.0 + 0.05 * torch.randn(shape[0], *([1] * (w.dim() - 1)), generator=g))
+        sd[base + ".weight_v"] = w
+    return sd
+
+
 def blob_checksum(blob):
     """Order-sensitive fingerprint of a float32 blob (guards golden fixtures against RNG drift)."""
     b = blob.detach().to(torch.float64)
