@@ -664,6 +664,59 @@ int32_t wetts_disc_losses(int32_t kind, int32_t n, const float* const* a_host, c
                           const int64_t* a_bs_host, const int64_t* g_bs_host, const int64_t* N_host, int32_t B,
                           float scale, double* sums, float* item_a, float* item_g, float* per_utt, float* total,
                           void* stream);
+/* n may be 1 .. WETTS_DISC_LOSSES_MAX_ITEMS: the row sums go out in groups of at most 40 items (an item's sums do not
+ * depend on its group), the totals launch reads the whole table. */
+#define WETTS_DISC_LOSSES_MAX_ITEMS 128
+
+/* ---- MultiPeriodMultiResolutionDiscriminator (csrc/mrd.hip) -------------------------------------------------------
+ *
+ * model/discriminators.py:127-225,256-283 without gradients: three DiscriminatorR stacks (window lengths 2048, 1024,
+ * 512; hop = window / 4; no embedding) followed by the five DiscriminatorP stacks; there is no DiscriminatorS.  The
+ * blob layout is fixed: `discriminators.{0,1,2}.band_convs.{b}.{l}.{weight,bias}` (b, l = 0..4, Conv2d weights
+ * [Cout, Cin, 3, kf]) and `discriminators.{0,1,2}.conv_post.*`, then `discriminators.{3..7}.convs.M.*` /
+ * `.conv_post.*` as in the period stacks of wetts_disc_t; weight norm folded.  216 tensors.  A handle of its own; create
+ * also builds the three window-folded DFT bases and packs the band convs' weights for the matrix cores. */
+typedef struct wetts_mrd wetts_mrd_t;
+#define WETTS_MRD_NUM_FMAPS 93
+#define WETTS_MRD_MIN_SAMPLES 1025 /* the centring reflect pad of the 2048 window needs T > 1024 */
+
+int32_t wetts_mrd_blob_num_tensors(void);
+int32_t wetts_mrd_blob_tensor_info(int32_t index, char* name_buf, size_t name_buf_len, int64_t* offset,
+                                   int64_t* numel, int64_t shape[4]);
+int64_t wetts_mrd_blob_numel(void);
+int32_t wetts_mrd_create(const float* blob_dev, int64_t blob_numel, void* stream, wetts_mrd_t** out);
+void wetts_mrd_destroy(wetts_mrd_t* d);
+
+/* Shape of feature map `index` (0..92) for B utterance PAIRS of T samples.  Resolution r (0..2) owns the maps
+ * 21 r .. 21 r + 20: band b's layers 1..4 at 21 r + 4 b + (layer - 1), each the reference's contiguous
+ * [2B][32][frames][F'], and conv_post at 21 r + 20, [2B][1][frames][sum F'].  The period stacks follow at 63 + 6 d + m
+ * in the internal shape {rows = 2B * p, C, H, p} of wetts_disc_fmap_shape.  frames = 1 + T / hop. */
+int32_t wetts_mrd_fmap_shape(int32_t B, int32_t T, int32_t index, int64_t shape[4]);
+/* Bytes of caller-provided scratch for wetts_mrd_forward: the normalised audio, one resolution's complex spectrogram
+ * and its layer-0 band outputs (none of them a returned map).  Negative on a bad argument. */
+int64_t wetts_mrd_workspace_bytes(int32_t B, int32_t T);
+/* All eight stacks on y and y_hat [B, 1, T] as one batch of 2B (real first).  fmaps_host: 93 device buffers of the
+ * shapes above, owned by the caller.  Allocates nothing.  T >= WETTS_MRD_MIN_SAMPLES. */
+int32_t wetts_mrd_forward(const wetts_mrd_t* d, const float* y, const float* y_hat, int32_t B, int32_t T,
+                          float* const* fmaps_host, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The stages of one DiscriminatorR on `rows` independent utterances, with the kernels and weights the forward pass
+ * uses.  normalize: y [rows][T] -> (0.8 (y - mean)) / (max |y - mean| + 1e-9), [rows][T].  spectrogram: the normalised
+ * audio -> the complex STFT of resolution `res` in the INTERNAL layout [rows][2][bins][frames] (re plane, im plane;
+ * frames fastest), bins = window / 2 + 1.  band_conv: layer 0..4 of all five bands in one launch; x holds the five
+ * bands' inputs one after another, each [rows][Cin][frames][Fin_b] (layer 0: x is the spectrogram itself), out the five
+ * outputs one after another, each [rows][32][frames][Fout_b].  conv_post: x as band_conv's layer-4 output,
+ * out [rows][1][frames][sum Fout_b]. */
+int32_t wetts_mrd_normalize(const float* y, int32_t rows, int32_t T, float* out, void* stream);
+int32_t wetts_mrd_spectrogram(const wetts_mrd_t* d, int32_t res, const float* x, int32_t rows, int32_t T, float* spec,
+                              void* stream);
+int32_t wetts_mrd_band_conv(const wetts_mrd_t* d, int32_t res, int32_t layer, const float* x, int32_t rows,
+                            int32_t frames, float* out, void* stream);
+int32_t wetts_mrd_conv_post(const wetts_mrd_t* d, int32_t res, const float* x, int32_t rows, int32_t frames,
+                            float* out, void* stream);
+/* Width of band `band` (0..4) of resolution `res` after `layer` convs (layer 0 = the band's bins, 5 = what conv_post
+ * reads): the reference's int(f * bins) edges and its conv arithmetic.  Negative on a bad argument. */
+int32_t wetts_mrd_band_width(int32_t res, int32_t band, int32_t layer);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,20 @@ SIGNATURES = {
     "wetts_disc_grouped_conv": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
     "wetts_disc_losses": (_I32, [_I32, _I32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64),
                                  C.POINTER(_I64), _I32, _F, _P, _P, _P, _P, _P, _P]),
+    "wetts_mrd_blob_num_tensors": (_I32, []),
+    "wetts_mrd_blob_tensor_info": (_I32, [_I32, C.c_char_p, C.c_size_t, C.POINTER(_I64), C.POINTER(_I64),
+                                          C.POINTER(_I64 * 4)]),
+    "wetts_mrd_blob_numel": (_I64, []),
+    "wetts_mrd_create": (_I32, [_P, _I64, _P, C.POINTER(_P)]),
+    "wetts_mrd_destroy": (None, [_P]),
+    "wetts_mrd_fmap_shape": (_I32, [_I32, _I32, _I32, C.POINTER(_I64 * 4)]),
+    "wetts_mrd_workspace_bytes": (_I64, [_I32, _I32]),
+    "wetts_mrd_forward": (_I32, [_P, _P, _P, _I32, _I32, C.POINTER(_P), _P, _I64, _P]),
+    "wetts_mrd_normalize": (_I32, [_P, _I32, _I32, _P, _P]),
+    "wetts_mrd_spectrogram": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
+    "wetts_mrd_band_conv": (_I32, [_P, _I32, _I32, _P, _I32, _I32, _P, _P]),
+    "wetts_mrd_conv_post": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
+    "wetts_mrd_band_width": (_I32, [_I32, _I32, _I32]),
 }
 
 # WETTS_STATUS_* bits of include/wetts_hip.h

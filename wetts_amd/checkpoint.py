@@ -243,6 +243,51 @@ def pack_disc_blob(state_dict):
     return blob
 
 
+def mrd_layout():
+    """[(name, offset, numel, shape)] of the MultiPeriodMultiResolutionDiscriminator's blob: the three DiscriminatorR
+    stacks (`discriminators.{0,1,2}.band_convs.B.L.*`, `.conv_post.*`) then the five period stacks
+    (`discriminators.{3..7}.convs.M.*`, `.conv_post.*`), weight norm folded, as the library defines it
+    (wetts_mrd_blob_tensor_info)."""
+    lib = _lib.load()
+    out = []
+    buf = C.create_string_buffer(256)
+    off, num, shape = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+    for i in range(lib.wetts_mrd_blob_num_tensors()):
+        _lib.check(lib.wetts_mrd_blob_tensor_info(i, buf, 256, C.byref(off), C.byref(num), C.byref(shape)),
+                   "mrd_blob_tensor_info")
+        shp = tuple(int(s) for s in shape if s > 0)
+        out.append((buf.value.decode(), int(off.value), int(num.value), shp))
+    return out
+
+
+def mrd_numel():
+    return int(_lib.load().wetts_mrd_blob_numel())
+
+
+def pack_mrd_blob(state_dict):
+    """Natural-layout float32 CPU blob of the MPMRD from a reference-keyed state_dict (a `D_*.pth`'s "model" of a recipe
+    with use_mrd_disc): weight-norm pairs in either spelling are folded.  Every tensor must be present and have its
+    layout shape.  A DiscriminatorR embedding (`discriminators.N.emb.weight`, num_embeddings) is not supported."""
+    emb = [k for k in state_dict if k.startswith("discriminators.") and ".emb." in k]
+    if emb:
+        raise NotImplementedError(f"DiscriminatorR's num_embeddings conditioning is not supported (found {emb[0]})")
+    sd = fold_weight_norm(state_dict)
+    blob = torch.zeros(mrd_numel(), dtype=torch.float32)
+    missing = []
+    for name, off, numel, shape in mrd_layout():
+        t = sd.get(name)
+        if t is None:
+            missing.append(name)
+            continue
+        t = t.detach().to(torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != expected {shape}")
+        blob[off:off + numel] = t.reshape(-1)
+    if missing:
+        raise KeyError(f"{len(missing)} discriminator tensors missing from checkpoint: {missing}")
+    return blob
+
+
 def load_state_dict_file(checkpoint_path):
     """Reads `G_*.pth` as saved by task.save_checkpoint (task.py:59-76): {"model": state_dict,
     "iteration", "optimizer", "learning_rate"}; a bare state_dict is accepted too."""

@@ -27,7 +27,6 @@ namespace wetts {
 typedef float f32x16d __attribute__((ext_vector_type(16)));
 
 constexpr float kSlope = 0.1f;  // modules.LRELU_SLOPE
-constexpr int kPeriods[5] = {2, 3, 5, 7, 11};
 constexpr int kNumDisc = 6, kNumFmaps = 37;  // S: 6 convs + conv_post, each P: 5 convs + conv_post
 
 __device__ __forceinline__ float lrelu(float v) { return v >= 0.f ? v : kSlope * v; }
@@ -256,11 +255,15 @@ grouped_conv1d_kernel(const float* __restrict__ x, const float* __restrict__ x2,
 // Reductions.  An item is one (real, generated) tensor pair whose utterance b owns the contiguous N floats at
 // a + b * a_bs / g + b * g_bs.  kind 0 (feature_loss): sum |a - g|.  kind 1 (discriminator_loss): sum (1 - a)^2 and
 // sum g^2.  kind 2 (generator_loss): sum (1 - a)^2 (g unused).  sums: [2][n][B] float64.
-constexpr int kMaxItems = 40;
+constexpr int kMaxItems = 40;  // per rows launch: 40 items are 1.6 KB of kernel arguments
+constexpr int kMaxLossItems = WETTS_DISC_LOSSES_MAX_ITEMS;
 struct LossItems {
   const float* a[kMaxItems];
   const float* g[kMaxItems];
   int64_t a_bs[kMaxItems], g_bs[kMaxItems], N[kMaxItems];
+};
+struct LossCounts {  // what the totals launch reads
+  int64_t N[kMaxLossItems];
 };
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -278,13 +281,14 @@ __device__ __forceinline__ double block_sum_d(double v, double* part) {
   return r;
 }
 
+// `it` holds the items i0 .. i0 + gridDim.y - 1 of the n (a group of a long list: an item's sums do not depend on it)
 __global__ void __launch_bounds__(256)
-disc_rows_kernel(LossItems it, int kind, int n, int B, double* __restrict__ sums) {
+disc_rows_kernel(LossItems it, int kind, int i0, int n, int B, double* __restrict__ sums) {
   __shared__ double part[4];
-  const int b = blockIdx.x, i = blockIdx.y;
-  const int64_t N = it.N[i];
-  const float* pa = it.a[i] + (int64_t)b * it.a_bs[i];
-  const float* pg = kind == 2 ? nullptr : it.g[i] + (int64_t)b * it.g_bs[i];
+  const int b = blockIdx.x, il = blockIdx.y, i = i0 + il;
+  const int64_t N = it.N[il];
+  const float* pa = it.a[il] + (int64_t)b * it.a_bs[il];
+  const float* pg = kind == 2 ? nullptr : it.g[il] + (int64_t)b * it.g_bs[il];
   double s0[4] = {0., 0., 0., 0.}, s1[4] = {0., 0., 0., 0.};
   int k = 0;
   for (int64_t e = threadIdx.x; e < N; e += 256, ++k) {
@@ -311,7 +315,7 @@ disc_rows_kernel(LossItems it, int kind, int n, int B, double* __restrict__ sums
 // item_a[i] = (sum_b sums[0][i][b]) / (B * N_i) (and item_g from sums[1], kind 1), total = scale * sum_i (item_a + item_g),
 // per_utt[b] = scale * sum_i (sums[0][i][b] + sums[1][i][b]) / N_i.  One wave.
 __global__ void __launch_bounds__(64)
-disc_totals_kernel(LossItems it, int kind, int n, int B, float scale, const double* __restrict__ sums,
+disc_totals_kernel(LossCounts it, int kind, int n, int B, float scale, const double* __restrict__ sums,
                    float* __restrict__ item_a, float* __restrict__ item_g, float* __restrict__ per_utt,
                    float* __restrict__ total) {
   double tot = 0.;
@@ -344,11 +348,6 @@ disc_totals_kernel(LossItems it, int kind, int n, int B, float scale, const doub
 
 // ---------------------------------------------------------------------------------------------
 // host side: the fixed architecture, its blob and the launchers
-struct DiscLayer {
-  int Cout, Cin, K, stride, pad, groups;
-  int64_t w_off, b_off;
-};
-
 struct DiscTensor {
   std::string name;
   int64_t offset, numel, shape[4];
@@ -407,30 +406,28 @@ namespace wetts {
 
 static int out_len(const DiscLayer& y, int Tin) { return (Tin + 2 * y.pad - y.K) / y.stride + 1; }
 
-static int32_t launch_fold_conv0(const wetts_disc* h, int d, const float* y, const float* y_hat, int split, int B2, int T,
-                                 float* out, hipStream_t s) {
-  const int p = kPeriods[d - 1];
-  const DiscLayer& l = disc_layout().layers[d][0];
+// The launchers take the layer and the blob its offsets index, so that every handle that owns period stacks runs them.
+static int32_t launch_fold_conv0(const DiscLayer& l, const float* blob, int p, const float* y, const float* y_hat, int split,
+                                 int B2, int T, float* out, hipStream_t s) {
   const int H0 = cdiv(T, p), H1 = out_len(l, H0);
   WETTS_REQUIRE(H0 * p - T < T, "disc: T=%d is too short for the reflect pad of period %d", T, p);
   WETTS_REQUIRE((int64_t)B2 * p <= 65535, "disc: 2B * p = %lld rows exceed one launch", (long long)B2 * p);
   hipLaunchKernelGGL(period_fold_conv0_kernel, dim3((unsigned)cdiv(H1, 64), (unsigned)(B2 * p)), dim3(64), 0, s, y, y_hat,
-                     split, T, p, H0, H1, (const float*)(h->blob + l.w_off), (const float*)(h->blob + l.b_off), out);
+                     split, T, p, H0, H1, blob + l.w_off, blob + l.b_off, out);
   WETTS_LAUNCH_CHECK();
   return WETTS_OK;
 }
 
-static int32_t launch_strided(const wetts_disc* h, int d, int m, const float* x, int64_t rows, int Hin, float* out,
+static int32_t launch_strided(const DiscLayer& l, const float* blob, const float* x, int64_t rows, int Hin, float* out,
                               hipStream_t s) {
-  const DiscLayer& l = disc_layout().layers[d][m];
   WETTS_REQUIRE(l.K == 5 && l.groups == 1 && l.Cin % kDCK == 0 && l.Cout % kDM == 0,
-                "disc: layer %d of discriminator %d is not an MFMA conv", m, d);
+                "disc: a %d -> %d conv of %d taps is not an MFMA conv", l.Cin, l.Cout, l.K);
   const int Hout = out_len(l, Hin);
   const int64_t ncols = rows * Hout;
   WETTS_REQUIRE(Hin >= 1 && ncols >= 1 && (ncols + kDN - 1) / kDN <= 0x7fffffff, "disc: bad strided conv extent");
   const dim3 grid((unsigned)((ncols + kDN - 1) / kDN), (unsigned)(l.Cout / kDM));
-  const float* w = h->blob + l.w_off;
-  const float* b = h->blob + l.b_off;
+  const float* w = blob + l.w_off;
+  const float* b = blob + l.b_off;
   if (l.stride == 3)
     hipLaunchKernelGGL(strided_conv_mfma_kernel<3>, grid, dim3(256), 0, s, x, w, b, out, ncols, l.Cin, l.Cout, Hin, Hout);
   else
@@ -439,12 +436,11 @@ static int32_t launch_strided(const wetts_disc* h, int d, int m, const float* x,
   return WETTS_OK;
 }
 
-static int32_t launch_post(const wetts_disc* h, int d, const float* x, int B2, int H, float* out, hipStream_t s) {
-  const int p = d == 0 ? 1 : kPeriods[d - 1];
-  const DiscLayer& l = disc_layout().layers[d][n_layers(d) - 1];
+static int32_t launch_post(const DiscLayer& l, const float* blob, int p, const float* x, int B2, int H, float* out,
+                           hipStream_t s) {
   WETTS_REQUIRE(H >= 1 && B2 >= 1 && (int64_t)B2 * p <= 65535, "disc: bad conv_post extent");
   hipLaunchKernelGGL(conv_post_kernel, dim3((unsigned)cdiv(H, 64), (unsigned)(B2 * p)), dim3(256), 0, s, x,
-                     (const float*)(h->blob + l.w_off), (const float*)(h->blob + l.b_off), l.Cin, H, p, out);
+                     blob + l.w_off, blob + l.b_off, l.Cin, H, p, out);
   WETTS_LAUNCH_CHECK();
   return WETTS_OK;
 }
@@ -470,13 +466,39 @@ static void fmap_shape(int B2, int T, int index, int64_t shape[4]) {
     d = 1 + (index - 7) / 6;
     m = (index - 7) % 6;
   }
-  const int p = d == 0 ? 1 : kPeriods[d - 1];
+  const int p = d == 0 ? 1 : kDiscPeriods[d - 1];
   int H = d == 0 ? T : cdiv(T, p);
   for (int i = 0; i <= m; ++i) H = out_len(disc_layout().layers[d][i], H);
   shape[0] = (int64_t)B2 * p;
   shape[1] = disc_layout().layers[d][m].Cout;
   shape[2] = H;
   shape[3] = p;
+}
+
+void disc_period_layer(int m, DiscLayer* l) {
+  *l = disc_layout().layers[1][m];
+  l->w_off = l->b_off = 0;
+}
+
+void disc_period_fmap_shape(const DiscLayer* layers, int p, int B2, int T, int m, int64_t shape[4]) {
+  int H = cdiv(T, p);
+  for (int i = 0; i <= m; ++i) H = out_len(layers[i], H);
+  shape[0] = (int64_t)B2 * p;
+  shape[1] = layers[m].Cout;
+  shape[2] = H;
+  shape[3] = p;
+}
+
+int32_t disc_period_stack(const DiscLayer* layers, const float* blob, int p, const float* y, const float* y_hat, int split,
+                          int B2, int T, float* const* f, hipStream_t s) {
+  int64_t shp[4];
+  WETTS_TRY(launch_fold_conv0(layers[0], blob, p, y, y_hat, split, B2, T, f[0], s));
+  for (int m = 1; m < 5; ++m) {
+    disc_period_fmap_shape(layers, p, B2, T, m - 1, shp);
+    WETTS_TRY(launch_strided(layers[m], blob, f[m - 1], (int64_t)B2 * p, (int)shp[2], f[m], s));
+  }
+  disc_period_fmap_shape(layers, p, B2, T, 4, shp);
+  return launch_post(layers[5], blob, p, f[4], B2, (int)shp[2], f[5], s);
 }
 
 }  // namespace wetts
@@ -537,20 +559,22 @@ int32_t wetts_disc_fmap_shape(int32_t B, int32_t T, int32_t index, int64_t shape
 int32_t wetts_disc_fold_conv0(const wetts_disc_t* h, int32_t d, const float* y, int32_t rows, int32_t T, float* out,
                               void* stream) {
   WETTS_REQUIRE(h && y && out && d >= 1 && d < kNumDisc && rows >= 1 && T >= 1, "disc_fold_conv0: bad argument");
-  return launch_fold_conv0(h, d, y, y, rows, rows, T, out, (hipStream_t)stream);
+  return launch_fold_conv0(disc_layout().layers[d][0], h->blob, kDiscPeriods[d - 1], y, y, rows, rows, T, out,
+                           (hipStream_t)stream);
 }
 
 int32_t wetts_disc_strided_conv(const wetts_disc_t* h, int32_t d, int32_t layer, const float* x, int64_t rows,
                                 int32_t Hin, float* out, void* stream) {
   WETTS_REQUIRE(h && x && out && d >= 0 && d < kNumDisc && layer >= 1 && layer < n_layers(d) - 1,
                 "disc_strided_conv: bad argument");
-  return launch_strided(h, d, layer, x, rows, Hin, out, (hipStream_t)stream);
+  return launch_strided(disc_layout().layers[d][layer], h->blob, x, rows, Hin, out, (hipStream_t)stream);
 }
 
 int32_t wetts_disc_conv_post(const wetts_disc_t* h, int32_t d, const float* x, int32_t rows, int32_t H, float* out,
                              void* stream) {
   WETTS_REQUIRE(h && x && out && d >= 0 && d < kNumDisc && rows >= 1, "disc_conv_post: bad argument");
-  return launch_post(h, d, x, rows, H, out, (hipStream_t)stream);
+  return launch_post(disc_layout().layers[d][n_layers(d) - 1], h->blob, d == 0 ? 1 : kDiscPeriods[d - 1], x, rows, H, out,
+                     (hipStream_t)stream);
 }
 
 int32_t wetts_disc_grouped_conv(const wetts_disc_t* h, int32_t layer, const float* x, int32_t rows, int32_t Tin,
@@ -566,7 +590,6 @@ int32_t wetts_disc_forward(const wetts_disc_t* h, const float* y, const float* y
   for (int i = 0; i < kNumFmaps; ++i) WETTS_REQUIRE(fmaps_host[i] != nullptr, "disc_forward: fmap %d is null", i);
   hipStream_t s = (hipStream_t)stream;
   const int B2 = 2 * B;
-  int64_t shp[4];
   // DiscriminatorS
   int Tin = T;
   for (int m = 0; m < 5; ++m) {
@@ -574,47 +597,47 @@ int32_t wetts_disc_forward(const wetts_disc_t* h, const float* y, const float* y
                              B2, Tin, fmaps_host[m], s));
     Tin = out_len(disc_layout().layers[0][m], Tin);
   }
-  WETTS_TRY(launch_strided(h, 0, 5, fmaps_host[4], B2, Tin, fmaps_host[5], s));
-  WETTS_TRY(launch_post(h, 0, fmaps_host[5], B2, Tin, fmaps_host[6], s));
+  WETTS_TRY(launch_strided(disc_layout().layers[0][5], h->blob, fmaps_host[4], B2, Tin, fmaps_host[5], s));
+  WETTS_TRY(launch_post(disc_layout().layers[0][6], h->blob, 1, fmaps_host[5], B2, Tin, fmaps_host[6], s));
   // DiscriminatorP x 5
-  for (int d = 1; d < kNumDisc; ++d) {
-    float* const* f = fmaps_host + 7 + 6 * (d - 1);
-    const int p = kPeriods[d - 1];
-    WETTS_TRY(launch_fold_conv0(h, d, y, y_hat, B, B2, T, f[0], s));
-    for (int m = 1; m < 5; ++m) {
-      fmap_shape(B2, T, 7 + 6 * (d - 1) + m - 1, shp);
-      WETTS_TRY(launch_strided(h, d, m, f[m - 1], (int64_t)B2 * p, (int)shp[2], f[m], s));
-    }
-    fmap_shape(B2, T, 7 + 6 * (d - 1) + 4, shp);
-    WETTS_TRY(launch_post(h, d, f[4], B2, (int)shp[2], f[5], s));
-  }
+  for (int d = 1; d < kNumDisc; ++d)
+    WETTS_TRY(disc_period_stack(disc_layout().layers[d], h->blob, kDiscPeriods[d - 1], y, y_hat, B, B2, T,
+                                fmaps_host + 7 + 6 * (d - 1), s));
   return WETTS_OK;
 }
 
 int32_t wetts_disc_losses(int32_t kind, int32_t n, const float* const* a_host, const float* const* g_host,
                           const int64_t* a_bs_host, const int64_t* g_bs_host, const int64_t* N_host, int32_t B, float scale,
                           double* sums, float* item_a, float* item_g, float* per_utt, float* total, void* stream) {
-  WETTS_REQUIRE(kind >= 0 && kind <= 2 && n >= 1 && n <= kMaxItems && B >= 1 && B <= 65535,
+  WETTS_REQUIRE(kind >= 0 && kind <= 2 && n >= 1 && n <= kMaxLossItems && B >= 1 && B <= 65535,
                 "disc_losses: kind=%d n=%d B=%d out of range", kind, n, B);
   WETTS_REQUIRE(a_host && a_bs_host && N_host && sums && item_a && per_utt && total, "null argument");
   WETTS_REQUIRE(kind == 2 || (g_host && g_bs_host), "disc_losses: the generated tensors are missing");
   WETTS_REQUIRE(kind != 1 || item_g, "disc_losses: item_g is null");
-  LossItems it;
-  memset(&it, 0, sizeof(it));
+  LossCounts cnt;
+  memset(&cnt, 0, sizeof(cnt));
   for (int i = 0; i < n; ++i) {
     WETTS_REQUIRE(a_host[i] && N_host[i] >= 1 && (kind == 2 || g_host[i]), "disc_losses: item %d is empty", i);
-    it.a[i] = a_host[i];
-    it.a_bs[i] = a_bs_host[i];
-    it.N[i] = N_host[i];
-    if (kind != 2) {
-      it.g[i] = g_host[i];
-      it.g_bs[i] = g_bs_host[i];
-    }
+    cnt.N[i] = N_host[i];
   }
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(disc_rows_kernel, dim3((unsigned)B, (unsigned)n), dim3(256), 0, s, it, kind, n, B, sums);
-  WETTS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(disc_totals_kernel, dim3(1), dim3(64), 0, s, it, kind, n, B, scale, (const double*)sums, item_a, item_g,
+  for (int i0 = 0; i0 < n; i0 += kMaxItems) {
+    const int m = n - i0 < kMaxItems ? n - i0 : kMaxItems;
+    LossItems it;
+    memset(&it, 0, sizeof(it));
+    for (int i = 0; i < m; ++i) {
+      it.a[i] = a_host[i0 + i];
+      it.a_bs[i] = a_bs_host[i0 + i];
+      it.N[i] = N_host[i0 + i];
+      if (kind != 2) {
+        it.g[i] = g_host[i0 + i];
+        it.g_bs[i] = g_bs_host[i0 + i];
+      }
+    }
+    hipLaunchKernelGGL(disc_rows_kernel, dim3((unsigned)B, (unsigned)m), dim3(256), 0, s, it, kind, i0, n, B, sums);
+    WETTS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(disc_totals_kernel, dim3(1), dim3(64), 0, s, cnt, kind, n, B, scale, (const double*)sums, item_a, item_g,
                      per_utt, total);
   WETTS_LAUNCH_CHECK();
   return WETTS_OK;

@@ -229,4 +229,25 @@ int32_t k_kl_loss(const float* z_p, const float* logs_q, const float* m_p, const
 int32_t k_l1_loss(const float* a, const float* b, int B, int64_t N, float weight, float* partials, float* per_utt,
                   float* total, hipStream_t s);
 
+// ---- DiscriminatorP stacks (discriminator.hip), shared by wetts_disc_t and wetts_mrd_t (mrd.hip) ----
+// one conv of a stack: its geometry and where its folded weight / bias sit in the owner's blob
+struct DiscLayer {
+  int Cout, Cin, K, stride, pad, groups;
+  int64_t w_off, b_off;
+};
+constexpr int kDiscPeriods[5] = {2, 3, 5, 7, 11};
+// geometry of layer m (0..5) of a period stack; the offsets are left to the caller
+void disc_period_layer(int m, DiscLayer* l);
+// {rows = B2 * p, C, H, p} of layer m's output for B2 utterances of T samples
+void disc_period_fmap_shape(const DiscLayer* layers, int p, int B2, int T, int m, int64_t shape[4]);
+// the six layers of one period stack on y / y_hat ([split] real then [B2 - split] generated utterances of T samples):
+// f[0..5] are the caller's feature maps, `layers` offsets index `blob`
+int32_t disc_period_stack(const DiscLayer* layers, const float* blob, int p, const float* y, const float* y_hat, int split,
+                          int B2, int T, float* const* f, hipStream_t s);
+
+// ---- complex STFT (stft.hip) for DiscriminatorR: center = True with the reflect pad of n_fft / 2 and no other pad,
+// win = n_fft, basis from wetts_stft_basis(n_fft, n_fft); out [rows][2][n_fft / 2 + 1][frames], frames = 1 + T / hop
+int32_t launch_stft_cplx(const float* audio, int rows, int T, int n_fft, int hop, const float* basis, int frames,
+                         float* out, hipStream_t s);
+
 }  // namespace wetts

@@ -18,7 +18,7 @@
 // reflections, each at the utterance's OWN length.  Samples past lengths[b] are never read; frames past the
 // utterance's frame count are written as zeros.  B operands are then read from LDS as sig[f * hop + k]; the LDS image
 // keeps the strip in rows of `hop` samples padded to an odd stride, so the 32 frames of one ds_read_b32 hit 32 banks.
-#include "common.h"
+#include "kernels.h"
 
 namespace wetts {
 
@@ -110,11 +110,12 @@ __device__ __forceinline__ int stft_frames(int64_t len, int n_fft, int hop, int 
   return (int)(1 + (padded - n_fft) / hop);
 }
 
-template <int NT>
-__global__ void __launch_bounds__(64 * kStftWaves)
-stft_mag_kernel(const float* __restrict__ audio, const int64_t* __restrict__ lengths, int64_t L, int strips,
-                int n_fft, int hop, int left, int kp, int p, int c, int fs, int stride, int mtiles, int T,
-                const float* __restrict__ basis, float* __restrict__ out) {
+// The body of both STFT kernels: geometry, staging and the MFMA loop are one text; CPLX selects the epilogue at compile
+// time (false: the magnitude, out [B][nb][T]; true: re and im planes, out [B][2][nb][T], im of bins 0 and N/2 = 0).
+template <int NT, bool CPLX>
+__device__ __forceinline__ void stft_body(const float* __restrict__ audio, const int64_t* __restrict__ lengths, int64_t L,
+                                          int strips, int n_fft, int hop, int left, int kp, int p, int c, int fs, int stride,
+                                          int mtiles, int T, const float* __restrict__ basis, float* __restrict__ out) {
   extern __shared__ float sig[];
   const int b = blockIdx.x / strips;
   const int f0 = (blockIdx.x % strips) * fs;
@@ -125,7 +126,8 @@ stft_mag_kernel(const float* __restrict__ audio, const int64_t* __restrict__ len
   int64_t len = lengths ? lengths[b] : L;
   if (len > L) len = L;  // never read past the row
   const int Tb = stft_frames(len, n_fft, hop, p, c);
-  float* ob = out + (int64_t)b * nb * T;
+  float* ob = out + (int64_t)b * (CPLX ? 2 : 1) * nb * T;
+  const int64_t imo = (int64_t)nb * T;  // CPLX: offset of the im plane
   const int nf = min(fs, T - f0);  // frames of the strip inside the output
   if (f0 >= Tb) {  // the whole strip is padding: zeros, nothing read (uniform over the block)
     if (mt < mtiles) {
@@ -133,7 +135,10 @@ stft_mag_kernel(const float* __restrict__ audio, const int64_t* __restrict__ len
         const int r = mt * 32 + i / nf, f = f0 + i % nf;
         if (r < n_fft) {
           const int bin = r == 1 ? n_fft / 2 : r / 2;
-          if (r < 2 || (r & 1) == 0) ob[(int64_t)bin * T + f] = 0.f;
+          if (r < 2 || (r & 1) == 0) {
+            ob[(int64_t)bin * T + f] = 0.f;
+            if (CPLX) ob[imo + (int64_t)bin * T + f] = 0.f;
+          }
         }
       }
     }
@@ -202,7 +207,17 @@ stft_mag_kernel(const float* __restrict__ audio, const int64_t* __restrict__ len
         const int r = mt * 32 + 8 * g + 4 * half + 2 * h;
         if (r >= n_fft) continue;
         const float re = acc[t][4 * g + 2 * h], im = acc[t][4 * g + 2 * h + 1];
-        if (r == 0) {
+        if (CPLX) {
+          if (r == 0) {  // rows 0 and 1 are Re 0 and Re N/2
+            ob[f] = valid ? re : 0.f;
+            ob[imo + f] = 0.f;
+            ob[(int64_t)(n_fft / 2) * T + f] = valid ? im : 0.f;
+            ob[imo + (int64_t)(n_fft / 2) * T + f] = 0.f;
+          } else {
+            ob[(int64_t)(r / 2) * T + f] = valid ? re : 0.f;
+            ob[imo + (int64_t)(r / 2) * T + f] = valid ? im : 0.f;
+          }
+        } else if (r == 0) {
           ob[f] = valid ? sqrtf(re * re + 1e-6f) : 0.f;
           ob[(int64_t)(n_fft / 2) * T + f] = valid ? sqrtf(im * im + 1e-6f) : 0.f;
         } else {
@@ -210,6 +225,24 @@ stft_mag_kernel(const float* __restrict__ audio, const int64_t* __restrict__ len
         }
       }
   }
+}
+
+template <int NT>
+__global__ void __launch_bounds__(64 * kStftWaves)
+stft_mag_kernel(const float* __restrict__ audio, const int64_t* __restrict__ lengths, int64_t L, int strips,
+                int n_fft, int hop, int left, int kp, int p, int c, int fs, int stride, int mtiles, int T,
+                const float* __restrict__ basis, float* __restrict__ out) {
+  stft_body<NT, false>(audio, lengths, L, strips, n_fft, hop, left, kp, p, c, fs, stride, mtiles, T, basis, out);
+}
+
+// The complex spectrogram of DiscriminatorR (torchaudio's Spectrogram(power=None)): the same frames, re and im stored.
+// Consecutive lanes hold consecutive frames, so the planes are kept frames-fastest and the stores stay coalesced; the band
+// conv that reads them resolves the layout while it stages.
+template <int NT>
+__global__ void __launch_bounds__(64 * kStftWaves)
+stft_cplx_kernel(const float* __restrict__ audio, int64_t L, int strips, int n_fft, int hop, int left, int kp, int c,
+                 int fs, int stride, int mtiles, int T, const float* __restrict__ basis, float* __restrict__ out) {
+  stft_body<NT, true>(audio, nullptr, L, strips, n_fft, hop, left, kp, 0, c, fs, stride, mtiles, T, basis, out);
 }
 
 // log(clamp(mel_basis @ spec, 1e-5)) (mel_processing.py:97-111); frames at or past frame_lengths[b] (if given) are
@@ -262,6 +295,32 @@ static int32_t stft_check(int n_fft, int hop, int win) {
   const StftGeom g = stft_geom(n_fft, hop, win);
   WETTS_REQUIRE(g.lds_floats <= 2 * kStftLdsCapFloats,
                 "stft: one frame of n_fft %d, hop %d does not fit the LDS strip", n_fft, hop);
+  return WETTS_OK;
+}
+
+int32_t launch_stft_cplx(const float* audio, int rows, int T, int n_fft, int hop, const float* basis, int frames,
+                         float* out, hipStream_t s) {
+  WETTS_TRY(stft_check(n_fft, hop, n_fft));
+  WETTS_REQUIRE(audio && basis && out && rows >= 1, "stft_cplx: bad argument");
+  WETTS_REQUIRE(T > n_fft / 2 && frames == 1 + T / hop, "stft_cplx: T=%d does not give %d frames of n_fft %d, hop %d", T,
+                frames, n_fft, hop);
+  const StftGeom g = stft_geom(n_fft, hop, n_fft);
+  const int strips = cdiv(frames, g.fs);
+  WETTS_REQUIRE((int64_t)rows * strips < (1ll << 31), "stft_cplx: batch too large");
+  const dim3 grid((unsigned)(rows * strips), (unsigned)cdiv(g.mtiles, kStftWaves));
+  const size_t lds = (size_t)g.lds_floats * sizeof(float);
+  if (g.nt == 2) {
+    static signed char opt[64];
+    if (lds > 64 * 1024) WETTS_REQUIRE(lds_opt_in((const void*)stft_cplx_kernel<2>, opt), "stft: LDS opt-in refused");
+    hipLaunchKernelGGL(stft_cplx_kernel<2>, grid, dim3(64 * kStftWaves), lds, s, audio, (int64_t)T, strips, n_fft, hop,
+                       g.left, g.kp, n_fft / 2, g.fs, g.stride, g.mtiles, frames, basis, out);
+  } else {
+    static signed char opt[64];
+    if (lds > 64 * 1024) WETTS_REQUIRE(lds_opt_in((const void*)stft_cplx_kernel<1>, opt), "stft: LDS opt-in refused");
+    hipLaunchKernelGGL(stft_cplx_kernel<1>, grid, dim3(64 * kStftWaves), lds, s, audio, (int64_t)T, strips, n_fft, hop,
+                       g.left, g.kp, n_fft / 2, g.fs, g.stride, g.mtiles, frames, basis, out);
+  }
+  WETTS_LAUNCH_CHECK();
   return WETTS_OK;
 }
 

@@ -5,7 +5,10 @@ maps and takes views; the arithmetic is the HIP kernels of csrc/discriminator.hi
 y and y_hat run as one batch of 2B utterances, so every weight is read once; the results do not depend on the pairing
 (an utterance's maps are a function of that utterance alone, bit for bit).  A period stack's feature map is computed as
 [2B, p, C, H] and handed back as the permuted view [2B, C, H, p] -- the reference's shape, no copy -- split into its real
-and generated halves."""
+and generated halves.
+
+MultiPeriodMultiResolutionDiscriminator (model/discriminators.py:256-283, the `use_mrd_disc` recipes) follows below with
+the same surface: three DiscriminatorR stacks (csrc/mrd.hip) in front of the same five period stacks."""
 import ctypes as C
 
 import torch
@@ -171,3 +174,130 @@ class MultiPeriodDiscriminator:
         return y_d_rs, y_d_gs, fmap_rs, fmap_gs
 
     __call__ = forward
+
+
+# ---- MultiPeriodMultiResolutionDiscriminator ----------------------------------------------------------------------------
+MRD_WINDOWS = (2048, 1024, 512)
+MRD_MIN_SAMPLES = 1025  # torch.stft(center=True) reflect-pads n_fft / 2 = 1024 samples on each side: T must exceed that
+MRD_N_FMAPS = 93  # three DiscriminatorR: 5 bands x layers 1..4 + conv_post; five DiscriminatorP: 5 convs + conv_post
+_MRD_R_MAPS = 21
+
+
+class MultiPeriodMultiResolutionDiscriminator(MultiPeriodDiscriminator):
+    """model/discriminators.py:256-283 (the `use_mrd_disc` recipes, e.g. vits2_vocos_v1): DiscriminatorR for the window
+    lengths 2048, 1024, 512 (discriminators.py:127-225, no embedding) followed by DiscriminatorP for the periods 2, 3, 5,
+    7, 11; there is no DiscriminatorS.  The same evaluation-only surface as MultiPeriodDiscriminator; the arithmetic is
+    csrc/mrd.hip, csrc/stft.hip's complex STFT and the period kernels of csrc/discriminator.hip.  `use_spectral_norm`
+    only ever reached the period stacks and is refused as it is there."""
+    MIN_SAMPLES = MRD_MIN_SAMPLES
+
+    def __init__(self, use_spectral_norm=False):
+        super().__init__(use_spectral_norm)
+        self.windows = MRD_WINDOWS
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Reference-keyed state_dict (`discriminators.{0,1,2}.band_convs.B.L.*` / `.conv_post.*`,
+        `discriminators.{3..7}.convs.M.*` / `.conv_post.*`; either weight-norm spelling, or folded weights)."""
+        self._blob = checkpoint.pack_mrd_blob(state_dict)
+        if self._device is not None:
+            self._create()
+        return self
+
+    def state_dict(self):
+        self._require_blob()
+        return {name: self._blob[off:off + numel].reshape(shape).clone()
+                for name, off, numel, shape in checkpoint.mrd_layout()}
+
+    def _create(self):
+        self._destroy()
+        lib = _lib.load()
+        with torch.cuda.device(self._device):
+            dev = self._blob.to(self._device)
+            h = C.c_void_p()
+            _lib.check(lib.wetts_mrd_create(_lib.ptr(dev), dev.numel(), _lib.current_stream_ptr(), C.byref(h)),
+                       "mrd_create")
+        self._handle = h
+
+    def _destroy(self):
+        if self._handle is not None:
+            _lib.load().wetts_mrd_destroy(self._handle)
+            self._handle = None
+
+    @staticmethod
+    def fmap_shapes(B, T):
+        """The 93 maps as the device computes them (wetts_mrd_fmap_shape): (2B, C, frames, F) for the DiscriminatorR
+        maps, which is the reference's own shape; (rows, C, H, p) for the period stacks."""
+        lib = _lib.load()
+        out, shp = [], (C.c_int64 * 4)()
+        for i in range(MRD_N_FMAPS):
+            _lib.check(lib.wetts_mrd_fmap_shape(int(B), int(T), i, C.byref(shp)), "mrd_fmap_shape")
+            out.append(tuple(int(v) for v in shp))
+        return out
+
+    def _check(self, y, y_hat):
+        if torch.is_tensor(y) and y.dim() == 3 and y.shape[2] < self.MIN_SAMPLES:
+            raise ValueError(f"T = {y.shape[2]} samples: the centring reflect pad of the 2048-sample window "
+                             f"(torch.stft, center=True) needs at least {self.MIN_SAMPLES}")
+        super()._check(y, y_hat)
+
+    def _run(self, y, y_hat):
+        """-> (buffers [93] as the device wrote them, B): DiscriminatorR maps [2B, C, frames, F], period maps
+        [2B, p, C, H] and [2B, 1, H, p]; maps and workspace are slices of one torch-owned allocation made for this call."""
+        self._check(y, y_hat)
+        y = y.to(torch.float32).contiguous()
+        y_hat = y_hat.to(torch.float32).contiguous()
+        B, _, T = y.shape
+        shapes = self._shapes.get((B, T))
+        if shapes is None:
+            shapes = self._shapes[(B, T)] = self.fmap_shapes(B, T)
+        lib = _lib.load()
+        offs, total = [], 0
+        for s in shapes:
+            offs.append(total)
+            total += (s[0] * s[1] * s[2] * (s[3] if len(offs) <= 3 * _MRD_R_MAPS else 1) + 63) // 64 * 64
+        ws_bytes = int(lib.wetts_mrd_workspace_bytes(B, T))
+        if ws_bytes < 0:
+            raise _lib.WettsError(f"mrd_workspace_bytes: {_lib.last_error()}")
+        flat = torch.empty(total + ws_bytes // 4, dtype=torch.float32, device=y.device)
+        bufs = []
+        for i, (s, off) in enumerate(zip(shapes, offs)):
+            if i < 3 * _MRD_R_MAPS:
+                bufs.append(flat[off:off + s[0] * s[1] * s[2] * s[3]].view(*s))
+                continue
+            rows, Cc, H, p = s
+            t = flat[off:off + rows * Cc * H]
+            bufs.append(t.view(2 * B, 1, H, p) if (i - 3 * _MRD_R_MAPS) % 6 == 5 else t.view(2 * B, p, Cc, H))
+        ws = flat[total:]
+        ptrs = (C.c_void_p * MRD_N_FMAPS)(*[b.data_ptr() for b in bufs])
+        with torch.cuda.device(y.device):
+            _lib.check(lib.wetts_mrd_forward(self._handle, _lib.ptr(y), _lib.ptr(y_hat), B, T, ptrs, _lib.ptr(ws), ws_bytes,
+                                             _lib.current_stream_ptr()), "mrd_forward")
+        return bufs, B
+
+    def forward(self, y, y_hat):
+        """discriminators.py:270-283 -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs): eight entries each.  A DiscriminatorR's
+        output stays 4-D, [B, 1, frames, sum F'], as the reference returns it; a period stack's is [B, N_d]."""
+        bufs, B = self._run(y, y_hat)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        i = 0
+        for d in range(8):
+            n = _MRD_R_MAPS if d < 3 else 6
+            maps = [b if (d < 3 or k == n - 1) else b.permute(0, 2, 3, 1) for k, b in enumerate(bufs[i:i + n])]
+            i += n
+            fmap_rs.append([m[:B] for m in maps])
+            fmap_gs.append([m[B:] for m in maps])
+            y_d_rs.append(maps[-1][:B] if d < 3 else maps[-1][:B].reshape(B, -1))
+            y_d_gs.append(maps[-1][B:] if d < 3 else maps[-1][B:].reshape(B, -1))
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+    __call__ = forward
+
+
+def from_hparams(hps):
+    """train.py:196-203: MultiPeriodMultiResolutionDiscriminator where hps.model.use_mrd_disc is set, else
+    MultiPeriodDiscriminator; both with hps.model.use_spectral_norm."""
+    model = hps.model
+    keys = model.keys() if hasattr(model, "keys") else model
+    sn = bool(model["use_spectral_norm"]) if "use_spectral_norm" in keys else False
+    mrd = "use_mrd_disc" in keys and bool(model["use_mrd_disc"])
+    return (MultiPeriodMultiResolutionDiscriminator if mrd else MultiPeriodDiscriminator)(sn)

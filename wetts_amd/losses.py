@@ -101,13 +101,16 @@ def _rows(t, like=None):
     return t.to(torch.float32).contiguous(), N, N
 
 
+MAX_ITEMS = 128  # WETTS_DISC_LOSSES_MAX_ITEMS: the MPMRD's 93 feature maps fit
+
+
 def _disc_reduce(kind, reals, gens, scale, what):
     """wetts_disc_losses over the tensor pairs -> (total [1], item_a [n], item_g [n], per_utt [B])."""
     reals = list(reals)
     gens = list(gens) if gens is not None else None
     n = len(reals)
-    if n < 1 or n > 40 or (gens is not None and len(gens) != n):
-        raise ValueError(f"{what}: needs 1 .. 40 tensors (and as many generated as real), got {n}")
+    if n < 1 or n > MAX_ITEMS or (gens is not None and len(gens) != n):
+        raise ValueError(f"{what}: needs 1 .. {MAX_ITEMS} tensors (and as many generated as real), got {n}")
     dev, B = None, None
     a, g = [], []
     for i in range(n):
@@ -192,10 +195,10 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
     hps.train.c_dur where the recipe has one, else 1), dur (unweighted) and dur_per_utt [B].  It costs one more
     read-back of the status word.
 
-    `net_d` (a MultiPeriodDiscriminator) with `y`, the batch's waveform [B, 1, T_wav], adds the adversarial terms of
+    `net_d` (a MultiPeriodDiscriminator or a MultiPeriodMultiResolutionDiscriminator) with `y`, the batch's waveform [B, 1, T_wav], adds the adversarial terms of
     train.py:431-439,480-491: y is sliced at ids_slice * hop, net_d(y_slice, y_hat) runs once, and the entries are
     loss_disc, loss_gen, loss_fm (scalars), loss_disc_per_utt, loss_gen_per_utt, loss_fm_per_utt [B], losses_disc_r,
-    losses_disc_g and losses_gen [6], and y_slice [B, 1, segment * hop].  Without `net_d` nothing changes."""
+    losses_disc_g and losses_gen (one per discriminator), and y_slice [B, 1, segment * hop].  Without `net_d` nothing changes."""
     d = hps.data
     if (net_d is None) != (y is None):
         raise ValueError("net_d and y (the batch's waveform [B, 1, T_wav]) go together")

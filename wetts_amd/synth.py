@@ -181,6 +181,25 @@ def make_discriminator_state_dict(seed=0):
     return sd
 
 
+def make_mrd_state_dict(seed=0):
+    """Reference-keyed state_dict of MultiPeriodMultiResolutionDiscriminator (discriminators.py:256-268) with old-style
+    weight-norm pairs on every conv, deterministic in `seed` from a generator of its own; values as
+    make_discriminator_state_dict gives them (fan_in = Cin * kh * kw for the Conv2d stacks)."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    for name, _, _, shape in checkpoint.mrd_layout():
+        base, kind = name.rsplit(".", 1)
+        if kind == "bias":
+            sd[name] = 0.05 * torch.randn(*shape, generator=g, dtype=torch.float32)
+            continue
+        fan_in = shape[1] * shape[2] * shape[3]
+        w = torch.randn(*shape, generator=g, dtype=torch.float32) * math.sqrt(2.0 / fan_in)
+        norm = torch.linalg.vector_norm(w, ord=2, dim=tuple(range(1, w.dim())), keepdim=True)
+        sd[base + ".weight_g"] = norm * (1.0 + 0.05 * torch.randn(shape[0], *([1] * (w.dim() - 1)), generator=g))
+        sd[base + ".weight_v"] = w
+    return sd
+
+
 def blob_checksum(blob):
     """Order-sensitive fingerprint of a float32 blob (guards golden fixtures against RNG drift)."""
     b = blob.detach().to(torch.float64)
