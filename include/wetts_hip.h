@@ -718,6 +718,51 @@ int32_t wetts_mrd_conv_post(const wetts_mrd_t* d, int32_t res, const float* x, i
  * reads): the reference's int(f * bins) edges and its conv arithmetic.  Negative on a bad argument. */
 int32_t wetts_mrd_band_width(int32_t res, int32_t band, int32_t layer);
 
+/* ---- VITS2 duration discriminators (csrc/duration_disc.hip) -------------------------------------------------------
+ *
+ * model/discriminators.py:287-449 without gradients.  version 1 = DurationDiscriminatorV1 (convs with bias only),
+ * 2 = DurationDiscriminatorV2 (ReLU and a channel LayerNorm behind every conv).  The blob holds, in this order,
+ * conv_1.{weight,bias} [norm_1.{gamma,beta}] conv_2.* [norm_2.*] dur_proj.* pre_out_conv_1.* [pre_out_norm_1.*]
+ * pre_out_conv_2.* [pre_out_norm_2.*] output_layer.0.{weight,bias}; the bracketed tensors in version 2 only (version 1
+ * constructs pre_out_norm_* and never reads them).  in_channels and filter_channels: multiples of 32 up to 256;
+ * kernel_size odd, up to 7; anything else is refused.  A handle of its own. */
+typedef struct wetts_durdisc wetts_durdisc_t;
+
+int32_t wetts_durdisc_blob_num_tensors(int32_t version, int32_t in_channels, int32_t filter_channels,
+                                       int32_t kernel_size);
+int32_t wetts_durdisc_blob_tensor_info(int32_t version, int32_t in_channels, int32_t filter_channels,
+                                       int32_t kernel_size, int32_t index, char* name_buf, size_t name_buf_len,
+                                       int64_t* offset, int64_t* numel, int64_t shape[4]);
+int64_t wetts_durdisc_blob_numel(int32_t version, int32_t in_channels, int32_t filter_channels, int32_t kernel_size);
+int32_t wetts_durdisc_create(int32_t version, int32_t in_channels, int32_t filter_channels, int32_t kernel_size,
+                             const float* blob_dev, int64_t blob_numel, void* stream, wetts_durdisc_t** out);
+void wetts_durdisc_destroy(wetts_durdisc_t* d);
+
+/* The workspace of wetts_durdisc_forward holds every stage, one after another, each rounded up to 64 floats:
+ * conv_1's map [B][F][Tx], conv_2's [B][F][Tx], pre_out_conv_1's [2B][F][Tx], pre_out_conv_2's [2B][F][Tx] (each after
+ * its ReLU + LayerNorm in version 2, before the next mask) and the probabilities [2B][Tx].  Rows 0..B-1 of the last
+ * three belong to dur_r, rows B..2B-1 to dur_hat.  Negative on a bad argument. */
+int64_t wetts_durdisc_workspace_bytes(const wetts_durdisc_t* d, int32_t B, int32_t Tx);
+/* x [B][in_channels][Tx] (not pre-masked), x_mask [B][Tx], dur_r and dur_hat [B][Tx].  Four launches; allocates
+ * nothing. */
+int32_t wetts_durdisc_forward(const wetts_durdisc_t* d, const float* x, const float* x_mask, const float* dur_r,
+                              const float* dur_hat, int32_t B, int32_t Tx, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+/* One layer with the kernel and weights the forward pass uses, on `rows` output rows.  layer 0 conv_1, 1 conv_2,
+ * 3 pre_out_conv_2: x [rows][C][Tx].  layer 2, pre_out_conv_1: x [src_rows][F][Tx] and dur [rows][Tx].  The row map:
+ * output row r reads mask row r mod src_rows (x_mask [src_rows][Tx]) and, in layer 2, x row r mod src_rows.
+ * out [rows][F][Tx]; prob [rows][Tx] is written by layer 3 only. */
+int32_t wetts_durdisc_layer(const wetts_durdisc_t* d, int32_t layer, const float* x, const float* x_mask,
+                            const float* dur, int32_t rows, int32_t src_rows, int32_t Tx, float* out, float* prob,
+                            void* stream);
+/* Row means of the probabilities prob_r, prob_g [B][Tx] in the reduction order of wetts_disc_losses (float64 sums, no
+ * atomics).  Over all Tx positions of row b, as losses.py's means count them: r_rows = mean (1 - r)^2, g_rows = mean
+ * g^2, gen_rows = mean (1 - g)^2.  Over the row's own positions (x_mask != 0): disc_per_utt = mean ((1 - r)^2 + g^2),
+ * gen_per_utt = mean (1 - g)^2; NaN for a row without any. */
+int32_t wetts_durdisc_row_means(const float* prob_r, const float* prob_g, const float* x_mask, int32_t B, int32_t Tx,
+                                float* r_rows, float* g_rows, float* gen_rows, float* disc_per_utt,
+                                float* gen_per_utt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

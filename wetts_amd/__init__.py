@@ -5,10 +5,13 @@ Only what the SynthesizerTrn.infer() hot path needs lives here.
 """
 from .config import HParams, get_hparams_from_file, make_config, MODEL_CONFIGS  # noqa: F401
 from .models import SynthesizerTrn, load_checkpoint  # noqa: F401
-from .discriminators import MultiPeriodDiscriminator, MultiPeriodMultiResolutionDiscriminator  # noqa: F401
+from .discriminators import (DurationDiscriminatorV1, DurationDiscriminatorV2,  # noqa: F401
+                             MultiPeriodDiscriminator, MultiPeriodMultiResolutionDiscriminator,
+                             duration_discriminator_from_hparams)
 from .mel_processing import (mel_spectrogram_torch, posterior_spectrogram, spec_to_mel_torch,  # noqa: F401
                              spectrogram_torch)
 
 __all__ = ["SynthesizerTrn", "MultiPeriodDiscriminator", "MultiPeriodMultiResolutionDiscriminator",
+           "DurationDiscriminatorV1", "DurationDiscriminatorV2", "duration_discriminator_from_hparams",
            "load_checkpoint", "HParams", "get_hparams_from_file", "make_config",
            "MODEL_CONFIGS", "spectrogram_torch", "spec_to_mel_torch", "mel_spectrogram_torch", "posterior_spectrogram"]

@@ -184,6 +184,16 @@ SIGNATURES = {
     "wetts_mrd_band_conv": (_I32, [_P, _I32, _I32, _P, _I32, _I32, _P, _P]),
     "wetts_mrd_conv_post": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
     "wetts_mrd_band_width": (_I32, [_I32, _I32, _I32]),
+    "wetts_durdisc_blob_num_tensors": (_I32, [_I32, _I32, _I32, _I32]),
+    "wetts_durdisc_blob_tensor_info": (_I32, [_I32, _I32, _I32, _I32, _I32, C.c_char_p, C.c_size_t, C.POINTER(_I64),
+                                              C.POINTER(_I64), C.POINTER(_I64 * 4)]),
+    "wetts_durdisc_blob_numel": (_I64, [_I32, _I32, _I32, _I32]),
+    "wetts_durdisc_create": (_I32, [_I32, _I32, _I32, _I32, _P, _I64, _P, C.POINTER(_P)]),
+    "wetts_durdisc_destroy": (None, [_P]),
+    "wetts_durdisc_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_durdisc_forward": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _I64, _P]),
+    "wetts_durdisc_layer": (_I32, [_P, _I32, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "wetts_durdisc_row_means": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
 }
 
 # WETTS_STATUS_* bits of include/wetts_hip.h

@@ -288,6 +288,55 @@ def pack_mrd_blob(state_dict):
     return blob
 
 
+def durdisc_layout(version, in_channels, filter_channels, kernel_size):
+    """[(name, offset, numel, shape)] of a duration discriminator's blob (model/discriminators.py:287-449; version 1 =
+    DurationDiscriminatorV1, 2 = DurationDiscriminatorV2), as the library defines it (wetts_durdisc_blob_tensor_info).
+    Version 1 has no norm tensors: the reference constructs `pre_out_norm_*` there and never reads them.  Raises
+    ValueError for a shape the kernel does not cover (channels: multiples of 32 up to 256; taps: odd, up to 7)."""
+    lib = _lib.load()
+    cfg = (int(version), int(in_channels), int(filter_channels), int(kernel_size))
+    n = lib.wetts_durdisc_blob_num_tensors(*cfg)
+    if n < 0:
+        raise ValueError(_lib.last_error())
+    out = []
+    buf = C.create_string_buffer(256)
+    off, num, shape = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+    for i in range(n):
+        _lib.check(lib.wetts_durdisc_blob_tensor_info(*cfg, i, buf, 256, C.byref(off), C.byref(num), C.byref(shape)),
+                   "durdisc_blob_tensor_info")
+        shp = tuple(int(s) for s in shape if s > 0)
+        out.append((buf.value.decode(), int(off.value), int(num.value), shp))
+    return out
+
+
+def durdisc_numel(version, in_channels, filter_channels, kernel_size):
+    n = int(_lib.load().wetts_durdisc_blob_numel(int(version), int(in_channels), int(filter_channels), int(kernel_size)))
+    if n < 0:
+        raise ValueError(_lib.last_error())
+    return n
+
+
+def pack_durdisc_blob(version, in_channels, filter_channels, kernel_size, state_dict):
+    """Natural-layout float32 CPU blob of a duration discriminator from a reference-keyed state_dict (a `DUR_*.pth`'s
+    "model").  Every tensor of the layout must be present and have its layout shape; tensors the version does not read
+    (version 1's `pre_out_norm_*`) are ignored."""
+    cfg = (version, in_channels, filter_channels, kernel_size)
+    blob = torch.zeros(durdisc_numel(*cfg), dtype=torch.float32)
+    missing = []
+    for name, off, numel, shape in durdisc_layout(*cfg):
+        t = state_dict.get(name)
+        if t is None:
+            missing.append(name)
+            continue
+        t = t.detach().to(torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != expected {shape}")
+        blob[off:off + numel] = t.reshape(-1)
+    if missing:
+        raise KeyError(f"{len(missing)} duration discriminator tensors missing from checkpoint: {missing}")
+    return blob
+
+
 def load_state_dict_file(checkpoint_path):
     """Reads `G_*.pth` as saved by task.save_checkpoint (task.py:59-76): {"model": state_dict,
     "iteration", "optimizer", "learning_rate"}; a bare state_dict is accepted too."""

@@ -8,7 +8,10 @@ y and y_hat run as one batch of 2B utterances, so every weight is read once; the
 and generated halves.
 
 MultiPeriodMultiResolutionDiscriminator (model/discriminators.py:256-283, the `use_mrd_disc` recipes) follows below with
-the same surface: three DiscriminatorR stacks (csrc/mrd.hip) in front of the same five period stacks."""
+the same surface: three DiscriminatorR stacks (csrc/mrd.hip) in front of the same five period stacks.
+
+DurationDiscriminatorV1 / DurationDiscriminatorV2 (model/discriminators.py:287-449, the `use_duration_discriminator`
+recipes) close the file: csrc/duration_disc.hip, four launches per call."""
 import ctypes as C
 
 import torch
@@ -301,3 +304,185 @@ def from_hparams(hps):
     sn = bool(model["use_spectral_norm"]) if "use_spectral_norm" in keys else False
     mrd = "use_mrd_disc" in keys and bool(model["use_mrd_disc"])
     return (MultiPeriodMultiResolutionDiscriminator if mrd else MultiPeriodDiscriminator)(sn)
+
+
+# ---- VITS2 duration discriminators ------------------------------------------------------------------------------------
+AVAILABLE_DURATION_DISCRIMINATOR_TYPES = ("dur_disc_1", "dur_disc_2")  # model/discriminators.py:15-18
+DURDISC_STAGES = ("conv_1", "conv_2", "pre_out_conv_1", "pre_out_conv_2", "prob")
+
+
+class DurationDiscriminatorV1:
+    """model/discriminators.py:287-369 as an evaluation module on the device: conv_1 and conv_2 on hidden_x, then per
+    duration dur_proj, the concatenation, pre_out_conv_1, pre_out_conv_2, Linear and sigmoid; every conv reads its
+    input under x_mask and pads with zeros at Tx.  The reference's constructor signature; `p_dropout` and
+    `gin_channels` are stored and unused, as there (the dropout is never applied, `cond` is commented out).  forward()
+    returns the reference's [prob_r, prob_g], each [B, Tx, 1]: losses.discriminator_loss zips over that pair's batch
+    rows, which losses.teacher_forced_losses(net_dur_disc=) reproduces.  `pre_out_norm_*` of a state_dict are ignored."""
+    VERSION = 1
+
+    def __init__(self, in_channels, filter_channels, kernel_size, p_dropout, gin_channels=0):
+        self.in_channels = int(in_channels)
+        self.filter_channels = int(filter_channels)
+        self.kernel_size = int(kernel_size)
+        self.p_dropout = p_dropout
+        self.gin_channels = gin_channels
+        self.training = False
+        self._cfg = (self.VERSION, self.in_channels, self.filter_channels, self.kernel_size)
+        checkpoint.durdisc_layout(*self._cfg)  # raises ValueError for a shape the kernel does not cover: no slow path
+        self._blob = None
+        self._handle = None
+        self._device = None
+
+    # ---- nn.Module-like surface ----
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("this discriminator is evaluation only (no gradients)")
+        return self
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Reference-keyed state_dict (a `DUR_*.pth`'s "model").  Every tensor the class reads must be present."""
+        self._blob = checkpoint.pack_durdisc_blob(*self._cfg, state_dict)
+        if self._device is not None:
+            self._create()
+        return self
+
+    def state_dict(self):
+        """The tensors the class uses, reference-keyed."""
+        self._require_blob()
+        return {name: self._blob[off:off + numel].reshape(shape).clone()
+                for name, off, numel, shape in checkpoint.durdisc_layout(*self._cfg)}
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"{type(self).__name__} runs on a HIP device only (there is no CPU path)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self._device = device
+        if self._blob is not None:
+            self._create()
+        return self
+
+    def cuda(self, device=None):
+        return self.to("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+
+    def _require_blob(self):
+        if self._blob is None:
+            raise RuntimeError("no weights: call load_state_dict() (or models.load_checkpoint on a DUR_*.pth) first")
+
+    def _create(self):
+        self._destroy()
+        lib = _lib.load()
+        with torch.cuda.device(self._device):
+            dev = self._blob.to(self._device)
+            h = C.c_void_p()
+            _lib.check(lib.wetts_durdisc_create(*self._cfg, _lib.ptr(dev), dev.numel(), _lib.current_stream_ptr(),
+                                                C.byref(h)), "durdisc_create")
+        self._handle = h
+
+    def _destroy(self):
+        if self._handle is not None:
+            _lib.load().wetts_durdisc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    def _require(self):
+        self._require_blob()
+        if self._handle is None:
+            raise RuntimeError("the discriminator is not on a device: call .to('cuda') / .cuda() first")
+
+    # ---- forward ----
+    def _check(self, x, x_mask, durs):
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError(f"x must be a [B, {self.in_channels}, Tx] tensor, got {getattr(x, 'shape', type(x))}")
+        B, _, Tx = x.shape
+        if B < 1 or Tx < 1:
+            raise ValueError("empty batch")
+        for t, n in ((x_mask, "x_mask"),) + tuple(durs):
+            if not torch.is_tensor(t) or tuple(t.shape) != (B, 1, Tx):
+                raise ValueError(f"{n} must be a [{B}, 1, {Tx}] tensor, got {getattr(t, 'shape', type(t))}")
+        for t, n in ((x, "x"), (x_mask, "x_mask")) + tuple(durs):
+            if t.device.type != "cuda":
+                raise ValueError(f"{n} must be on a HIP device (there is no CPU path)")
+        self._require()
+        for t, n in ((x, "x"), (x_mask, "x_mask")) + tuple(durs):
+            if t.device != self._device:
+                raise ValueError(f"{n} is on {t.device}, the discriminator on {self._device}")
+
+    def _run(self, x, x_mask, dur_r, dur_hat):
+        """-> the five stages as the device wrote them (DURDISC_STAGES): conv_1's and conv_2's maps [B, F, Tx],
+        pre_out_conv_1's and pre_out_conv_2's [2B, F, Tx] (version 2: after ReLU + LayerNorm; rows 0..B-1 belong to
+        dur_r) and the probabilities [2B, Tx]; all slices of one torch-owned allocation made for this call."""
+        self._check(x, x_mask, ((dur_r, "dur_r"), (dur_hat, "dur_hat")))
+        x, x_mask, dur_r, dur_hat = (t.to(torch.float32).contiguous() for t in (x, x_mask, dur_r, dur_hat))
+        B, _, Tx = x.shape
+        F_ = self.filter_channels
+        lib = _lib.load()
+        nbytes = int(lib.wetts_durdisc_workspace_bytes(self._handle, B, Tx))
+        if nbytes < 0:
+            raise _lib.WettsError(f"durdisc_workspace_bytes: {_lib.last_error()}")
+        flat = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.wetts_durdisc_forward(self._handle, _lib.ptr(x), _lib.ptr(x_mask), _lib.ptr(dur_r),
+                                                 _lib.ptr(dur_hat), B, Tx, _lib.ptr(flat), nbytes,
+                                                 _lib.current_stream_ptr()), "durdisc_forward")
+        out, off = [], 0
+        for shape in ((B, F_, Tx), (B, F_, Tx), (2 * B, F_, Tx), (2 * B, F_, Tx), (2 * B, Tx)):
+            n = 1
+            for v in shape:
+                n *= v
+            out.append(flat[off:off + n].view(*shape))
+            off += (n + 63) // 64 * 64
+        return out
+
+    def _probs(self, x, x_mask, dur_r, dur_hat):
+        prob = self._run(x, x_mask, dur_r, dur_hat)[4]
+        B = x.shape[0]
+        return prob[:B].unsqueeze(2), prob[B:].unsqueeze(2)
+
+    def forward(self, x, x_mask, dur_r, dur_hat, g=None):
+        """discriminators.py:350-369 -> [prob_r, prob_g], each [B, Tx, 1].  `g` is accepted and unused, as there."""
+        return list(self._probs(x, x_mask, dur_r, dur_hat))
+
+    def forward_probability(self, x, x_mask, dur, g=None):
+        """The probabilities [B, Tx, 1] of one duration tensor.  `x` is hidden_x, as in forward(): the trunk runs here
+        too (the reference's method of this name takes the trunk's output, which this module does not hand out)."""
+        return self._probs(x, x_mask, dur, dur)[0]
+
+    __call__ = forward
+
+
+class DurationDiscriminatorV2(DurationDiscriminatorV1):
+    """model/discriminators.py:372-449: ReLU and a channel LayerNorm (normalization.py: biased variance over the
+    channels, eps 1e-5) behind each of the four convs.  forward() returns the reference's [[prob_r], [prob_g]], over
+    which losses.discriminator_loss forms ONE term (the mean over B * Tx)."""
+    VERSION = 2
+
+    def forward(self, x, x_mask, dur_r, dur_hat, g=None):
+        """discriminators.py:432-449 -> [[prob_r], [prob_g]], each probability tensor [B, Tx, 1]."""
+        r, g_ = self._probs(x, x_mask, dur_r, dur_hat)
+        return [[r], [g_]]
+
+    __call__ = forward
+
+
+def duration_discriminator_from_hparams(hps):
+    """train.py:129-163: None unless hps.model.use_duration_discriminator; else the class named by
+    hps.model.duration_discriminator_type (default "dur_disc_1"), built as (hidden_channels, hidden_channels, 3, 0.1,
+    gin_channels = hps.model.gin_channels where hps.data.n_speakers != 0, else 0)."""
+    model = hps.model
+    if not ("use_duration_discriminator" in model.keys() and model["use_duration_discriminator"]):
+        return None
+    kind = model["duration_discriminator_type"] if "duration_discriminator_type" in model.keys() else "dur_disc_1"
+    assert kind in AVAILABLE_DURATION_DISCRIMINATOR_TYPES, kind
+    cls = DurationDiscriminatorV1 if kind == "dur_disc_1" else DurationDiscriminatorV2
+    gin = model["gin_channels"] if hps.data["n_speakers"] != 0 else 0
+    return cls(model["hidden_channels"], model["hidden_channels"], 3, 0.1, gin_channels=gin)

@@ -171,12 +171,37 @@ def generator_loss(disc_outputs, *, per_utterance=False):
     return (total[0], gl, per_utt) if per_utterance else (total[0], gl)
 
 
+def _duration_disc_losses(net_dur_disc, x_enc, x_mask, logw_, logw):
+    """train.py:441-453,481-495 on one call of the duration discriminator -> the entries teacher_forced_losses adds.
+    The reference's zip over what the class returns decides the terms: DurationDiscriminatorV1 hands back two tensors,
+    so discriminator_loss / generator_loss iterate over their BATCH ROWS -- B terms, each a mean over one utterance's Tx
+    padded positions, summed: B x the one-mean value, which the reducer's `scale` carries.  DurationDiscriminatorV2
+    hands back two one-element lists: one term over B * Tx."""
+    B, _, Tx = x_enc.shape
+    prob_r, prob_g = net_dur_disc._probs(x_enc, x_mask.reshape(B, 1, Tx), logw_.reshape(B, 1, Tx), logw.reshape(B, 1, Tx))
+    mask = _f32(x_mask.reshape(B, Tx), "x_mask", 2, prob_r.device)
+    r_rows, g_rows, gen_rows, disc_pu, gen_pu = (torch.empty(B, dtype=torch.float32, device=prob_r.device)
+                                                 for _ in range(5))
+    with torch.cuda.device(prob_r.device):
+        _lib.check(_lib.load().wetts_durdisc_row_means(_lib.ptr(prob_r), _lib.ptr(prob_g), _lib.ptr(mask), B, Tx,
+                                                       _lib.ptr(r_rows), _lib.ptr(g_rows), _lib.ptr(gen_rows),
+                                                       _lib.ptr(disc_pu), _lib.ptr(gen_pu), _lib.current_stream_ptr()),
+                   "durdisc_row_means")
+    per_row = getattr(net_dur_disc, "VERSION", 2) == 1
+    scale = float(B) if per_row else 1.0
+    disc, r1, g1, _ = _disc_reduce(1, [prob_r], [prob_g], scale, "duration discriminator_loss")
+    gen, n1, _, _ = _disc_reduce(2, [prob_g], None, scale, "duration generator_loss")
+    return dict(loss_dur_disc=disc[0], losses_dur_disc_r=r_rows if per_row else r1,
+                losses_dur_disc_g=g_rows if per_row else g1, loss_dur_gen=gen[0],
+                losses_dur_gen=gen_rows if per_row else n1, dur_disc_per_utt=disc_pu, dur_gen_per_utt=gen_pu)
+
+
 def _flag(section, key):
     return key in section.keys() and bool(section[key])
 
 
 def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None, with_duration=False, e_q=None,
-                          eps_w=None, net_d=None, y=None, **reconstruct_kwargs):
+                          eps_w=None, net_d=None, y=None, net_dur_disc=None, **reconstruct_kwargs):
     """train.py:400-432,486-488 for one batch, without gradients: net_g.reconstruct(...) in the place of net_g(...), the
     target mel (`spec` itself for a mel posterior encoder, else spec_to_mel_torch(spec)) sliced at ids_slice, the mel
     spectrogram of the decoded slice, and
@@ -198,8 +223,18 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
     `net_d` (a MultiPeriodDiscriminator or a MultiPeriodMultiResolutionDiscriminator) with `y`, the batch's waveform [B, 1, T_wav], adds the adversarial terms of
     train.py:431-439,480-491: y is sliced at ids_slice * hop, net_d(y_slice, y_hat) runs once, and the entries are
     loss_disc, loss_gen, loss_fm (scalars), loss_disc_per_utt, loss_gen_per_utt, loss_fm_per_utt [B], losses_disc_r,
-    losses_disc_g and losses_gen (one per discriminator), and y_slice [B, 1, segment * hop].  Without `net_d` nothing changes."""
+    losses_disc_g and losses_gen (one per discriminator), and y_slice [B, 1, segment * hop].  Without `net_d` nothing changes.
+
+    `net_dur_disc` (a DurationDiscriminatorV1 or V2; needs `with_duration=True`, whose stage supplies x_enc, x_mask,
+    logw_ and logw) adds train.py:441-453,481-495: net_dur_disc(x_enc, x_mask, logw_, logw) runs once, and the entries
+    are loss_dur_disc, loss_dur_gen (scalars), losses_dur_disc_r, losses_dur_disc_g, losses_dur_gen -- the reference's
+    values for the class in use: B terms and their sum for V1, whose two returned tensors the reference's zip walks row
+    by row (each term a mean over ALL Tx positions, as train.py:446 notes), one term for V2 -- and dur_disc_per_utt,
+    dur_gen_per_utt [B]: each utterance's mean over its own phonemes, which does not depend on the batch (NaN for an
+    utterance without any).  Without `net_dur_disc` nothing changes."""
     d = hps.data
+    if net_dur_disc is not None and not with_duration:
+        raise ValueError("net_dur_disc needs with_duration=True: its inputs are that stage's x_enc, x_mask, logw_ and logw")
     if (net_d is None) != (y is None):
         raise ValueError("net_d and y (the batch's waveform [B, 1, T_wav]) go together")
     if int(net_g.hop_length) != int(d.hop_length):
@@ -227,6 +262,9 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
         c_dur = float(hps.train.c_dur) if "c_dur" in hps.train.keys() else 1.0
         dur = net_g._duration_from_recon(e_q, eps_w, c_dur)
         out.update(loss_dur=dur["total"][1], dur=dur["total"][0], dur_per_utt=dur["per_utt"])
+        if net_dur_disc is not None:
+            out.update(_duration_disc_losses(net_dur_disc, net_g._last_recon["x_enc"], dur["x_mask"], dur["logw_"],
+                                             dur["logw"]))
     if net_d is not None:
         y_slice = commons.slice_segments(y, ids_slice, seg, scale=int(net_g.hop_length))
         y_d_r, y_d_g, fmap_r, fmap_g = net_d(y_slice, o)

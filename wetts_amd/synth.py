@@ -200,6 +200,42 @@ def make_mrd_state_dict(seed=0):
     return sd
 
 
+def make_duration_discriminator_state_dict(version, seed=0, in_channels=192, filter_channels=192, kernel_size=3):
+    """Reference-keyed state_dict of DurationDiscriminatorV1 (version 1) or V2 (version 2) (discriminators.py:287-449) as
+    a `DUR_*.pth` holds it, deterministic in `seed` from a generator of its own.  Weights randn * fan_in ** -0.5, biases
+    0.05 * randn, gamma = 1 + 0.1 * randn, beta = 0.1 * randn: with unit-variance inputs the probabilities stay away from
+    0 and 1, so a parity test measures something.  Version 1 carries the `pre_out_norm_*` tensors its class constructs
+    and never reads."""
+    if version not in (1, 2):
+        raise ValueError(f"version must be 1 or 2, got {version!r}")
+    g = torch.Generator().manual_seed(int(seed))
+    F_, K = int(filter_channels), int(kernel_size)
+    sd = {}
+
+    def conv(name, cout, cin, k):
+        sd[name + ".weight"] = torch.randn(cout, cin, k, generator=g, dtype=torch.float32) * float(cin * k) ** -0.5
+        sd[name + ".bias"] = 0.05 * torch.randn(cout, generator=g, dtype=torch.float32)
+
+    def norm(name):
+        sd[name + ".gamma"] = 1.0 + 0.1 * torch.randn(F_, generator=g, dtype=torch.float32)
+        sd[name + ".beta"] = 0.1 * torch.randn(F_, generator=g, dtype=torch.float32)
+
+    conv("conv_1", F_, int(in_channels), K)
+    if version == 2:
+        norm("norm_1")
+    conv("conv_2", F_, F_, K)
+    if version == 2:
+        norm("norm_2")
+    conv("dur_proj", F_, 1, 1)
+    conv("pre_out_conv_1", F_, 2 * F_, K)
+    norm("pre_out_norm_1")
+    conv("pre_out_conv_2", F_, F_, K)
+    norm("pre_out_norm_2")
+    sd["output_layer.0.weight"] = torch.randn(1, F_, generator=g, dtype=torch.float32) * float(F_) ** -0.5
+    sd["output_layer.0.bias"] = 0.05 * torch.randn(1, generator=g, dtype=torch.float32)
+    return sd
+
+
 def blob_checksum(blob):
     """Order-sensitive fingerprint of a float32 blob (guards golden fixtures against RNG drift)."""
     b = blob.detach().to(torch.float64)
