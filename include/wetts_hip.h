@@ -56,6 +56,8 @@ extern "C" {
 #define WETTS_STATUS_DURATION_NEGATIVE 32 /* a negative frame count given to wetts_counts_to_lengths */
 #define WETTS_STATUS_SEGMENT_LONGER 64    /* wetts_slice_ids: an utterance shorter than the decoder segment, or a given
                                            * slice id outside [0, len - segment] (the reference slices out of range) */
+#define WETTS_STATUS_TOKEN_ID_RANGE 128   /* wetts_frontend_*: a token id outside [0, vocab_size) (nn.Embedding IndexError) */
+#define WETTS_STATUS_TYPE_ID_RANGE 256    /* wetts_frontend_*: a token type id outside [0, type_vocab_size) */
 
 #define WETTS_MAX_STAGES 8
 #define WETTS_MAX_RB_KERNELS 8
@@ -762,6 +764,73 @@ int32_t wetts_durdisc_layer(const wetts_durdisc_t* d, int32_t layer, const float
 int32_t wetts_durdisc_row_means(const float* prob_r, const float* prob_g, const float* x_mask, int32_t B, int32_t Tx,
                                 float* r_rows, float* g_rows, float* gen_rows, float* disc_per_utt,
                                 float* gen_per_utt, void* stream);
+
+/* ---- the text frontend (frontend/model.py:21-73; csrc/frontend.hip) ------------------------------------------------
+ * An HF BertModel (absolute positions, last_hidden_state only), one nn.TransformerEncoderLayer(batch_first) at its
+ * defaults (post-norm, ReLU, eps 1e-5, packed in_proj) and the two Linear classifiers, without gradients, f32
+ * throughout.  A blob and a handle of its own.  The blob holds the reference's state_dict tensors under their own keys
+ * (bert.embeddings.*, bert.encoder.layer.N.*, transform.*, phone_classifier.*, prosody_classifier.*) in natural layout,
+ * each at a multiple of 4 floats; bert.pooler.* and position_ids are not part of it.
+ * Limits: hidden_size a multiple of 8 up to 1024; heads of at most 96 channels (BERT's and transform's);
+ * intermediate_size and transform_ff multiples of 8; T <= min(max_position_embeddings, 512).
+ * Activations are token-major: [B * T][channels]. */
+typedef struct wetts_frontend_config {
+  int32_t vocab_size, hidden_size, num_layers, num_heads, intermediate_size, max_position_embeddings, type_vocab_size;
+  float layer_norm_eps;                  /* BERT's LayerNorms (1e-12) */
+  int32_t transform_heads, transform_ff; /* the TransformerEncoderLayer: 8 / 2048 at 768, 12 / 1200 at 312 */
+  int32_t num_polyphones, num_prosody;
+} wetts_frontend_config_t;
+typedef struct wetts_frontend wetts_frontend_t;
+
+#define WETTS_FRONTEND_EPI_BIAS 0     /* x W^T + b */
+#define WETTS_FRONTEND_EPI_GELU 1     /* gelu(x W^T + b), the exact erf form */
+#define WETTS_FRONTEND_EPI_RELU 2     /* relu(x W^T + b) */
+#define WETTS_FRONTEND_EPI_RESIDUAL 3 /* x W^T + b + residual */
+
+int32_t wetts_frontend_blob_num_tensors(const wetts_frontend_config_t* cfg);
+int32_t wetts_frontend_blob_tensor_info(const wetts_frontend_config_t* cfg, int32_t index, char* name_buf,
+                                        size_t name_buf_len, int64_t* offset, int64_t* numel, int64_t shape[4]);
+int64_t wetts_frontend_blob_numel(const wetts_frontend_config_t* cfg);
+int32_t wetts_frontend_create(const wetts_frontend_config_t* cfg, const float* blob_dev, int64_t blob_numel, void* stream,
+                              wetts_frontend_t** out);
+void wetts_frontend_destroy(wetts_frontend_t* f);
+/* Bytes of scratch wetts_frontend_forward / _layer need for B rows of T tokens; negative on a bad argument. */
+int64_t wetts_frontend_workspace_bytes(const wetts_frontend_t* f, int32_t B, int32_t T);
+/* input_ids [B][T]; token_type_ids [B][T] or NULL (zeros); attention_mask [B][T] or NULL (ones): a key with mask 0 is
+ * excluded from every attention.  phone_out [B][T][num_polyphones] and prosody_out [B][T][num_prosody]: the logits, or
+ * with softmax != 0 the probabilities over the last dimension; ZEROS at a token whose mask is 0.  A token or type id
+ * outside its table ORs WETTS_STATUS_TOKEN_ID_RANGE / _TYPE_ID_RANGE into *status (device int32, may be NULL) and
+ * reads row 0.  T > max_position_embeddings, B < 1 and T < 1 are refused before any launch.  Allocates nothing. */
+int32_t wetts_frontend_forward(const wetts_frontend_t* f, const int64_t* input_ids, const int64_t* token_type_ids,
+                               const int64_t* attention_mask, int32_t B, int32_t T, int32_t softmax, float* phone_out,
+                               float* prosody_out, void* workspace, int32_t* status, void* stream);
+/* The stages, each with the kernel the forward pass uses.
+ * _embed: word + position + type, LayerNorm -> out [B * T][hidden]; mask_out [B * T] is the mask as 1.0 / 0.0.
+ * _linear: out [N][M] = x [N][K] weight[M][K]^T + bias, then WETTS_FRONTEND_EPI_*; K % 8 == 0, M % 4 == 0.
+ * _add_layer_norm: out = LayerNorm(x + residual) over C (residual may be NULL; out may be x).
+ * _attention: qkv [B * T][3 * heads * dk] (q | k | v) -> out [B * T][heads * dk], scores / sqrt(dk), keys with
+ *   key_mask [B * T] == 0 excluded; a row without any valid key gives zeros.
+ * _heads: x [N][hidden] -> both classifiers (and both softmaxes) in one launch; zeros where key_mask is 0.
+ * _layer: layer `layer` (0 .. num_layers - 1 the BERT layers, num_layers = transform) in place on x [B * T][hidden]. */
+int32_t wetts_frontend_embed(const wetts_frontend_t* f, const int64_t* input_ids, const int64_t* token_type_ids,
+                             const int64_t* attention_mask, int32_t B, int32_t T, float* out, float* mask_out,
+                             int32_t* status, void* stream);
+int32_t wetts_frontend_linear(const float* x, const float* weight, const float* bias, const float* residual, int32_t N,
+                              int32_t K, int32_t M, int32_t epilogue, float* out, void* stream);
+int32_t wetts_frontend_add_layer_norm(const float* x, const float* residual, const float* gamma, const float* beta,
+                                      float eps, int32_t N, int32_t C, float* out, void* stream);
+int32_t wetts_frontend_attention(const float* qkv, const float* key_mask, int32_t B, int32_t T, int32_t heads, int32_t dk,
+                                 float* out, void* stream);
+int32_t wetts_frontend_heads(const wetts_frontend_t* f, const float* x, const float* key_mask, int32_t N, int32_t softmax,
+                             float* phone_out, float* prosody_out, void* stream);
+int32_t wetts_frontend_layer(const wetts_frontend_t* f, int32_t layer, float* x, const float* key_mask, int32_t B,
+                             int32_t T, void* workspace, void* stream);
+/* The decisions of cli/frontend.py:70-81 per token: choice[n] = the index i of the FIRST candidate class
+ * cand[n][i], i < cand_len[n] <= max_cand, with the largest phone probability (0 without candidates); prosody[n] = the
+ * LOWEST class with the largest prosody probability. */
+int32_t wetts_frontend_decide(const float* phone_prob, const float* prosody_prob, const int32_t* cand,
+                              const int32_t* cand_len, int32_t N, int32_t P, int32_t R, int32_t max_cand, int32_t* choice,
+                              int32_t* prosody, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,10 +8,12 @@ from .models import SynthesizerTrn, load_checkpoint  # noqa: F401
 from .discriminators import (DurationDiscriminatorV1, DurationDiscriminatorV2,  # noqa: F401
                              MultiPeriodDiscriminator, MultiPeriodMultiResolutionDiscriminator,
                              duration_discriminator_from_hparams)
+from .frontend import Frontend, FrontendModel, FrontendSession, Model  # noqa: F401
 from .mel_processing import (mel_spectrogram_torch, posterior_spectrogram, spec_to_mel_torch,  # noqa: F401
                              spectrogram_torch)
 
 __all__ = ["SynthesizerTrn", "MultiPeriodDiscriminator", "MultiPeriodMultiResolutionDiscriminator",
            "DurationDiscriminatorV1", "DurationDiscriminatorV2", "duration_discriminator_from_hparams",
+           "FrontendModel", "FrontendSession", "Frontend", "Model",
            "load_checkpoint", "HParams", "get_hparams_from_file", "make_config",
            "MODEL_CONFIGS", "spectrogram_torch", "spec_to_mel_torch", "mel_spectrogram_torch", "posterior_spectrogram"]

@@ -73,6 +73,17 @@ _I64 = C.c_int64
 _F = C.c_float
 _CFG = C.POINTER(Config)
 
+
+class FrontendConfig(C.Structure):
+    """Mirror of wetts_frontend_config_t."""
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden_size", "num_layers", "num_heads", "intermediate_size",
+                                          "max_position_embeddings", "type_vocab_size")] + \
+               [("layer_norm_eps", C.c_float)] + \
+               [(n, C.c_int32) for n in ("transform_heads", "transform_ff", "num_polyphones", "num_prosody")]
+
+
+_FCFG = C.POINTER(FrontendConfig)
+
 # name -> (restype, argtypes); must list every symbol include/wetts_hip.h declares
 SIGNATURES = {
     "wetts_abi_version": (_I32, []),
@@ -194,11 +205,27 @@ SIGNATURES = {
     "wetts_durdisc_forward": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _I64, _P]),
     "wetts_durdisc_layer": (_I32, [_P, _I32, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "wetts_durdisc_row_means": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "wetts_frontend_blob_num_tensors": (_I32, [_FCFG]),
+    "wetts_frontend_blob_tensor_info": (_I32, [_FCFG, _I32, C.c_char_p, C.c_size_t, C.POINTER(_I64), C.POINTER(_I64),
+                                               C.POINTER(_I64 * 4)]),
+    "wetts_frontend_blob_numel": (_I64, [_FCFG]),
+    "wetts_frontend_create": (_I32, [_FCFG, _P, _I64, _P, C.POINTER(_P)]),
+    "wetts_frontend_destroy": (None, [_P]),
+    "wetts_frontend_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_frontend_forward": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "wetts_frontend_embed": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "wetts_frontend_linear": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    "wetts_frontend_add_layer_norm": (_I32, [_P, _P, _P, _P, _F, _I32, _I32, _P, _P]),
+    "wetts_frontend_attention": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    "wetts_frontend_heads": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "wetts_frontend_layer": (_I32, [_P, _I32, _P, _P, _I32, _I32, _P, _P]),
+    "wetts_frontend_decide": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
 }
 
 # WETTS_STATUS_* bits of include/wetts_hip.h
 STATUS_SPLINE_DOMAIN, STATUS_PHONE_ID_RANGE, STATUS_SPEAKER_ID_RANGE, STATUS_DURATION_NONFINITE = 1, 2, 4, 8
 STATUS_ALIGN_TEXT_LONGER, STATUS_DURATION_NEGATIVE, STATUS_SEGMENT_LONGER = 16, 32, 64
+STATUS_TOKEN_ID_RANGE, STATUS_TYPE_ID_RANGE = 128, 256
 
 _lib = None
 

@@ -337,6 +337,64 @@ def pack_durdisc_blob(version, in_channels, filter_channels, kernel_size, state_
     return blob
 
 
+def frontend_c_config(cfg):
+    """_lib.FrontendConfig of a frontend config dict (the fields of wetts_frontend_config_t)."""
+    c = _lib.FrontendConfig()
+    for name, _ in _lib.FrontendConfig._fields_:
+        if name not in cfg:
+            raise ValueError(f"frontend config: field {name!r} is missing")
+        setattr(c, name, float(cfg[name]) if name == "layer_norm_eps" else int(cfg[name]))
+    return c
+
+
+def frontend_layout(cfg):
+    """[(name, offset, numel, shape)] of the frontend's blob (frontend/model.py:21-73: an HF BertModel, `transform`, the
+    two classifiers), as the library defines it (wetts_frontend_blob_tensor_info); the names are the reference's
+    state_dict keys.  Raises ValueError for a config the kernels do not cover."""
+    lib = _lib.load()
+    c = frontend_c_config(cfg)
+    n = lib.wetts_frontend_blob_num_tensors(C.byref(c))
+    if n < 0:
+        raise ValueError(_lib.last_error())
+    out = []
+    buf = C.create_string_buffer(256)
+    off, num, shape = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+    for i in range(n):
+        _lib.check(lib.wetts_frontend_blob_tensor_info(C.byref(c), i, buf, 256, C.byref(off), C.byref(num), C.byref(shape)),
+                   "frontend_blob_tensor_info")
+        shp = tuple(int(v) for v in shape if v > 0)
+        out.append((buf.value.decode(), int(off.value), int(num.value), shp))
+    return out
+
+
+def frontend_numel(cfg):
+    c = frontend_c_config(cfg)
+    n = int(_lib.load().wetts_frontend_blob_numel(C.byref(c)))
+    if n < 0:
+        raise ValueError(_lib.last_error())
+    return n
+
+
+def pack_frontend_blob(cfg, state_dict):
+    """Natural-layout float32 CPU blob of the frontend from what frontend/train.py:215 saves (keys bert.*, transform.*,
+    phone_classifier.*, prosody_classifier.*).  Every tensor of the layout must be present and have its layout shape;
+    bert.pooler.* and bert.embeddings.position_ids are not read."""
+    blob = torch.zeros(frontend_numel(cfg), dtype=torch.float32)
+    missing = []
+    for name, off, numel, shape in frontend_layout(cfg):
+        t = state_dict.get(name)
+        if t is None:
+            missing.append(name)
+            continue
+        t = t.detach().to(torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != expected {shape}")
+        blob[off:off + numel] = t.reshape(-1)
+    if missing:
+        raise KeyError(f"{len(missing)} frontend tensors missing from checkpoint: {missing}")
+    return blob
+
+
 def load_state_dict_file(checkpoint_path):
     """Reads `G_*.pth` as saved by task.save_checkpoint (task.py:59-76): {"model": state_dict,
     "iteration", "optimizer", "learning_rate"}; a bare state_dict is accepted too."""

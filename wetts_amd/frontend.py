@@ -1,0 +1,432 @@
+"""The text frontend on the device: the reference's BERT polyphone / prosody model (frontend/model.py:21-73), its exported
+graph's session (frontend/export_onnx.py:72-91), cli/frontend.py's `Frontend` and cli/model.py's `Model`.
+
+    front = Frontend(front_dir)                       # final.pt + config.json + vocab.txt + lexicon/
+    model = Model(InferenceSession(net_g), phone_table, speaker_table, front)
+    phonemes, audio = model.synthesis("今天天气怎么样", "default")
+
+Everything between the string and the samples runs in csrc/frontend.hip and the existing synthesis path; there is no
+CPU inference, no onnxruntime and no `transformers` import.  Evaluation only (no gradients).
+
+Padded positions: the reference leaves whatever its torch build computes at a token whose attention_mask is 0; here both
+outputs are ZEROS there."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, checkpoint
+
+# frontend/model.py:33-42: substring of bert_name_or_path -> (d_model, nhead, dim_feedforward) of `transform`
+TRANSFORM_SHAPES = (("bert-chinese-base", (768, 8, 2048)), ("TinyBERT_4L_zh_backup", (312, 12, 1200)))
+
+
+def transform_shape(bert_name_or_path):
+    """The reference's rule; raises ValueError for a name it would `assert False` on."""
+    for key, shape in TRANSFORM_SHAPES:
+        if key in str(bert_name_or_path):
+            return shape
+    raise ValueError(f"unsupport model {bert_name_or_path!r}: the reference knows "
+                     f"{[k for k, _ in TRANSFORM_SHAPES]} (pass transform_heads= and transform_ff= for another BERT)")
+
+
+def frontend_config(num_polyphones, num_prosody, bert_config, transform_heads=None, transform_ff=None,
+                    bert_name_or_path=None):
+    """The config dict of wetts_frontend_config_t from an HF BERT `config.json` (dict or path)."""
+    if isinstance(bert_config, (str, os.PathLike)):
+        with open(bert_config, encoding="utf-8") as f:
+            bert_config = json.load(f)
+    bc = dict(bert_config)
+    if bc.get("hidden_act", "gelu") != "gelu":
+        raise ValueError(f"hidden_act = {bc['hidden_act']!r} is not supported (only \"gelu\", the exact erf form)")
+    if bc.get("position_embedding_type", "absolute") != "absolute":
+        raise ValueError(f"position_embedding_type = {bc['position_embedding_type']!r} is not supported (only \"absolute\")")
+    for k in ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size",
+              "max_position_embeddings"):
+        if k not in bc:
+            raise ValueError(f"bert_config has no {k!r}")
+    d = int(bc["hidden_size"])
+    if transform_heads is None or transform_ff is None:
+        name = bert_name_or_path if bert_name_or_path is not None else bc.get("_name_or_path", "")
+        dm, nh, ff = transform_shape(name)
+        if dm != d:
+            raise ValueError(f"{name!r} selects a transform of d_model {dm}, but hidden_size is {d}")
+        transform_heads = nh if transform_heads is None else transform_heads
+        transform_ff = ff if transform_ff is None else transform_ff
+    return dict(vocab_size=int(bc["vocab_size"]), hidden_size=d, num_layers=int(bc["num_hidden_layers"]),
+                num_heads=int(bc["num_attention_heads"]), intermediate_size=int(bc["intermediate_size"]),
+                max_position_embeddings=int(bc["max_position_embeddings"]), type_vocab_size=int(bc.get("type_vocab_size", 2)),
+                layer_norm_eps=float(bc.get("layer_norm_eps", 1e-12)), transform_heads=int(transform_heads),
+                transform_ff=int(transform_ff), num_polyphones=int(num_polyphones), num_prosody=int(num_prosody))
+
+
+class FrontendModel:
+    """frontend/model.py's FrontendModel as an evaluation module on the device.  `bert_config`: an HF config.json (dict
+    or path); `transform`'s heads and feed-forward width follow the reference's rule on bert_config["_name_or_path"] (or
+    `bert_name_or_path=`) unless given."""
+
+    def __init__(self, num_polyphones, num_prosody, bert_config, transform_heads=None, transform_ff=None,
+                 bert_name_or_path=None):
+        self.config = frontend_config(num_polyphones, num_prosody, bert_config, transform_heads, transform_ff,
+                                      bert_name_or_path)
+        checkpoint.frontend_layout(self.config)  # raises ValueError for a shape the kernels do not cover: no slow path
+        self.num_polyphones, self.num_prosody = self.config["num_polyphones"], self.config["num_prosody"]
+        self.training = False
+        self._blob = None
+        self._handle = None
+        self._device = None
+        self._status = None
+
+    # ---- nn.Module-like surface ----
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("the frontend is evaluation only (no gradients)")
+        return self
+
+    def load_state_dict(self, state_dict, strict=True):
+        """What frontend/train.py:215 saves.  Every tensor the model reads must be present with its shape; the pooler
+        and position_ids are ignored."""
+        self._blob = checkpoint.pack_frontend_blob(self.config, state_dict)
+        if self._device is not None:
+            self._create()
+        return self
+
+    def state_dict(self):
+        """The tensors the model uses, reference-keyed."""
+        self._require_blob()
+        return {name: self._blob[off:off + numel].reshape(shape).clone()
+                for name, off, numel, shape in checkpoint.frontend_layout(self.config)}
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("FrontendModel runs on a HIP device only (there is no CPU path)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self._device = device
+        if self._blob is not None:
+            self._create()
+        return self
+
+    def cuda(self, device=None):
+        return self.to("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+
+    @property
+    def device(self):
+        return self._device
+
+    def _require_blob(self):
+        if self._blob is None:
+            raise RuntimeError("no weights: call load_state_dict() first")
+
+    def _create(self):
+        self._destroy()
+        lib = _lib.load()
+        with torch.cuda.device(self._device):
+            dev = self._blob.to(self._device)
+            h = C.c_void_p()
+            cfg = checkpoint.frontend_c_config(self.config)
+            _lib.check(lib.wetts_frontend_create(C.byref(cfg), _lib.ptr(dev), dev.numel(), _lib.current_stream_ptr(),
+                                                 C.byref(h)), "frontend_create")
+            self._status = torch.zeros(1, dtype=torch.int32, device=self._device)
+        self._handle = h
+
+    def _destroy(self):
+        if self._handle is not None:
+            _lib.load().wetts_frontend_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    def _require(self):
+        self._require_blob()
+        if self._handle is None:
+            raise RuntimeError("the frontend is not on a device: call .to('cuda') / .cuda() first")
+
+    # ---- forward ----
+    def _inputs(self, ids, token_type_ids, attention_mask):
+        """-> (ids, token types or None, mask or None) as contiguous int64 tensors on the model's device; host checks."""
+        self._require()
+        ids = torch.as_tensor(ids)
+        if ids.dim() != 2 or ids.dtype in (torch.float16, torch.float32, torch.float64, torch.bfloat16):
+            raise ValueError(f"input_ids must be an integer [B, T] tensor, got {ids.dtype} {tuple(ids.shape)}")
+        B, T = ids.shape
+        if B < 1 or T < 1:
+            raise ValueError(f"input_ids {tuple(ids.shape)}: B and T must be at least 1")
+        if T > self.config["max_position_embeddings"]:
+            raise ValueError(f"T = {T} exceeds the {self.config['max_position_embeddings']} positions of the table")
+        out = []
+        for t, n in ((ids, "input_ids"), (token_type_ids, "token_type_ids"), (attention_mask, "attention_mask")):
+            if t is None:
+                out.append(None)
+                continue
+            t = torch.as_tensor(t)
+            if tuple(t.shape) != (B, T):
+                raise ValueError(f"{n} must be [{B}, {T}], got {tuple(t.shape)}")
+            out.append(t.to(device=self._device, dtype=torch.int64).contiguous())
+        return out
+
+    def _raise_status(self, bits):
+        if bits & _lib.STATUS_TOKEN_ID_RANGE:
+            raise IndexError("index out of range in self: a token id is outside [0, vocab_size)")
+        if bits & _lib.STATUS_TYPE_ID_RANGE:
+            raise IndexError("index out of range in self: a token type id is outside [0, type_vocab_size)")
+
+    def _launch(self, ids, tt, mask, softmax):
+        """One forward pass; no read-back.  -> (phone [B, T, P], prosody [B, T, R]) device tensors; the status word is
+        left for the caller (forward() reads it; Frontend reads it with the decisions)."""
+        B, T = ids.shape
+        lib = _lib.load()
+        nbytes = int(lib.wetts_frontend_workspace_bytes(self._handle, B, T))
+        if nbytes < 0:
+            raise _lib.WettsError(f"frontend_workspace_bytes: {_lib.last_error()}")
+        with torch.cuda.device(self._device):
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self._device)
+            phone = torch.empty(B, T, self.num_polyphones, dtype=torch.float32, device=self._device)
+            pros = torch.empty(B, T, self.num_prosody, dtype=torch.float32, device=self._device)
+            self._status.zero_()
+            _lib.check(lib.wetts_frontend_forward(self._handle, _lib.ptr(ids), _lib.ptr(tt), _lib.ptr(mask), B, T,
+                                                  1 if softmax else 0, _lib.ptr(phone), _lib.ptr(pros), _lib.ptr(ws),
+                                                  _lib.ptr(self._status), _lib.current_stream_ptr()), "frontend_forward")
+        return phone, pros
+
+    def _run(self, ids, token_type_ids, attention_mask, softmax):
+        ids, tt, mask = self._inputs(ids, token_type_ids, attention_mask)
+        phone, pros = self._launch(ids, tt, mask, softmax)
+        self._raise_status(int(self._status.item()))  # the one read-back of the call
+        return phone, pros
+
+    def forward(self, x):
+        """frontend/model.py:52-63 -> (phone_logits [B, T, P], prosody_logits [B, T, R]); x["token_type_ids"] (zeros)
+        and x["attention_mask"] (ones) are optional."""
+        return self._run(x["input_ids"], x.get("token_type_ids"), x.get("attention_mask"), False)
+
+    __call__ = forward
+
+    def export_forward(self, x):
+        """frontend/model.py:65-73: [1, T] ids -> the two softmaxes."""
+        assert x.shape[0] == 1
+        return self._run(x, None, None, True)
+
+    def probs(self, ids, attention_mask=None):
+        """export_forward for a padded batch: [B, T] ids and mask -> the two softmaxes (zeros at padded tokens)."""
+        return self._run(ids, None, attention_mask, True)
+
+    def decide(self, ids, attention_mask, cand, cand_len):
+        """One forward pass and cli/frontend.py:70-81's decisions on the device, ONE read-back: cand [B, T, max_cand]
+        int32 class ids and cand_len [B, T] -> (choice [B, T], prosody [B, T]) as numpy int32: the index of the first
+        candidate of the largest probability, and the lowest prosody class of the largest probability."""
+        ids, _, mask = self._inputs(ids, None, attention_mask)
+        B, T = ids.shape
+        cand = torch.as_tensor(cand, dtype=torch.int32)
+        if cand.dim() != 3 or tuple(cand.shape[:2]) != (B, T) or cand.shape[2] < 1:
+            raise ValueError(f"cand must be [{B}, {T}, max_cand], got {tuple(cand.shape)}")
+        cand_len = torch.as_tensor(cand_len, dtype=torch.int32)
+        if tuple(cand_len.shape) != (B, T):
+            raise ValueError(f"cand_len must be [{B}, {T}], got {tuple(cand_len.shape)}")
+        cand, cand_len = cand.to(self._device).contiguous(), cand_len.to(self._device).contiguous()
+        phone, pros = self._launch(ids, None, mask, True)
+        out = torch.empty(2 * B * T + 1, dtype=torch.int32, device=self._device)
+        with torch.cuda.device(self._device):
+            _lib.check(_lib.load().wetts_frontend_decide(_lib.ptr(phone), _lib.ptr(pros), _lib.ptr(cand), _lib.ptr(cand_len),
+                                                         B * T, self.num_polyphones, self.num_prosody, cand.shape[2],
+                                                         _lib.ptr(out[:B * T]), _lib.ptr(out[B * T:2 * B * T]),
+                                                         _lib.current_stream_ptr()), "frontend_decide")
+            out[2 * B * T:] = self._status
+        host = out.cpu().numpy()
+        self._raise_status(int(host[-1]))
+        return host[:B * T].reshape(B, T), host[B * T:2 * B * T].reshape(B, T)
+
+
+def load_frontend_model(model_dir, device="cuda"):
+    """FrontendModel from `final.pt` (frontend/train.py:215's state_dict) and `config.json` (the BERT's HF config) in
+    model_dir.  The classifier widths are read from the checkpoint."""
+    sd = torch.load(os.path.join(model_dir, "final.pt"), map_location="cpu", weights_only=True)
+    for k in ("phone_classifier.weight", "prosody_classifier.weight"):
+        if k not in sd:
+            raise KeyError(f"{k} missing from {os.path.join(model_dir, 'final.pt')}")
+    model = FrontendModel(sd["phone_classifier.weight"].shape[0], sd["prosody_classifier.weight"].shape[0],
+                          os.path.join(model_dir, "config.json"))
+    return model.load_state_dict(sd).to(device)
+
+
+class _Arg:
+    def __init__(self, name, shape, type_):
+        self.name, self.shape, self.type = name, shape, type_
+
+
+class FrontendSession:
+    """onnxruntime-shaped session of the frontend's exported graph (export_onnx.py:72-91): input `input` [1, T] int64,
+    outputs `polyphone_output` [1, T, P] and `prosody_output` [1, T, R], the two softmaxes of export_forward."""
+
+    def __init__(self, model_or_dir, device="cuda"):
+        self.model = model_or_dir if isinstance(model_or_dir, FrontendModel) else load_frontend_model(model_or_dir, device)
+        self.model._require()
+
+    def get_inputs(self):
+        return [_Arg("input", [1, "T"], "tensor(int64)")]
+
+    def get_outputs(self):
+        return [_Arg("polyphone_output", [1, "T", self.model.num_polyphones], "tensor(float)"),
+                _Arg("prosody_output", [1, "T", self.model.num_prosody], "tensor(float)")]
+
+    def run(self, output_names, feeds, run_options=None):
+        names = [o.name for o in self.get_outputs()]
+        if output_names is not None and any(n not in names for n in output_names):
+            raise ValueError(f"unknown output among {output_names}: the graph has {names}")
+        ids = torch.as_tensor(np.asarray(feeds["input"]), dtype=torch.int64)
+        outs = dict(zip(names, (t.cpu().numpy() for t in self.model.export_forward(ids))))
+        return [outs[n] for n in (names if output_names is None else output_names)]
+
+
+def host_decisions(pinyin_prob, prosody_prob, cands):
+    """cli/frontend.py:70-81 on host arrays, literally: pinyin_prob [T, P], prosody_prob [T, R], cands[i] the class ids of
+    token i's candidates -> ([index of the chosen candidate per token], [prosody class per token])."""
+    choice = []
+    for i, arr in enumerate(cands):
+        if len(arr) > 1:
+            poly_probs = [pinyin_prob[i][c] for c in arr]
+            choice.append(poly_probs.index(max(poly_probs)))
+        else:
+            choice.append(0)
+    return choice, np.asarray(prosody_prob).argmax(axis=1).tolist()
+
+
+class Frontend:
+    """cli/frontend.py's Frontend: the same table readers, the same compute(text).  model_dir holds `final.pt` and
+    `config.json` (nothing here reads `final.onnx`), `vocab.txt` and `lexicon/{polyphone.txt, pinyin_dict.txt,
+    lexicon.txt}`.  `session=`: any object with the exported graph's run() (then the decisions are the reference's host
+    code on its outputs); by default the model runs on the device and the decisions are made there too."""
+
+    def __init__(self, model_dir, session=None, device="cuda"):
+        self.token2id = self.read_list(os.path.join(model_dir, "vocab.txt"))
+        self.polyphone2id = self.read_list(os.path.join(model_dir, "lexicon", "polyphone.txt"))
+        self.id2polyphone = {v: k for k, v in self.polyphone2id.items()}
+        self.char2pinyins = self.read_char2pinyins(os.path.join(model_dir, "lexicon", "pinyin_dict.txt"))
+        self.pinyin2phones = self.read_pinyin2phones(os.path.join(model_dir, "lexicon", "lexicon.txt"))
+        self.model = None
+        if session is None:
+            self.model = load_frontend_model(model_dir, device)
+            if self.model.num_polyphones != len(self.polyphone2id):
+                raise ValueError(f"final.pt classifies {self.model.num_polyphones} polyphones, polyphone.txt lists "
+                                 f"{len(self.polyphone2id)}")
+            session = FrontendSession(self.model)
+        self.session = session
+
+    def read_list(self, fname):
+        table = {}
+        with open(fname, encoding="utf-8") as fin:
+            for i, line in enumerate(fin):
+                table[line.strip()] = i
+        return table
+
+    def read_char2pinyins(self, fname):
+        table = {}
+        with open(fname, encoding="utf-8") as fin:
+            for line in fin:
+                arr = line.split()
+                assert len(arr) == 2
+                table[arr[0]] = arr[1].split(",")
+        return table
+
+    def read_pinyin2phones(self, fname):
+        table = {}
+        with open(fname, encoding="utf-8") as fin:
+            for line in fin:
+                arr = line.split()
+                assert len(arr) >= 2
+                table[arr[0]] = arr[1:]
+        return table
+
+    def _tokens(self, text):
+        """-> (token ids, per token the candidate pinyins ([] for [CLS] / [SEP])); KeyError like the reference."""
+        tokens = ["[CLS]"] + [str(x) for x in text] + ["[SEP]"]
+        ids = [self.token2id[x] for x in tokens]
+        return ids, [[]] + [self.char2pinyins[x] for x in tokens[1:-1]] + [[]]
+
+    def _phonemes(self, arrs, choice, prosodys):
+        """cli/frontend.py:82-86 from the decisions of one text (all tokens, [CLS] and [SEP] included)."""
+        outputs = ["sil"]
+        for i in range(1, len(arrs) - 1):
+            outputs.extend(self.pinyin2phones[arrs[i][choice[i]]])
+            outputs.append("#{}".format(prosodys[i - 1]))  # the reference indexes the prosody from [CLS]'s row
+        outputs[-1] = "#4"
+        return outputs
+
+    def compute(self, text):
+        if self.model is not None:
+            return self.compute_batch([text])[0]
+        ids, arrs = self._tokens(text)
+        outputs = self.session.run(None, {"input": np.expand_dims(np.array(ids), axis=0)})
+        cands = [[self.polyphone2id[p] for p in a] if len(a) > 1 else [] for a in arrs]
+        choice, prosodys = host_decisions(outputs[0][0], outputs[1][0], cands)
+        return self._phonemes(arrs, choice, prosodys)
+
+    def compute_batch(self, texts):
+        """compute() of every text; with the device model: one padded forward pass, the decisions on the device and one
+        read-back for the whole list."""
+        texts = list(texts)
+        if self.model is None or not texts:
+            return [self.compute(t) for t in texts]
+        toks = [self._tokens(t) for t in texts]
+        B, T = len(toks), max(len(ids) for ids, _ in toks)
+        K = max([len(a) for _, arrs in toks for a in arrs] + [1])
+        ids = np.zeros((B, T), np.int64)
+        mask = np.zeros((B, T), np.int64)
+        cand = np.full((B, T, K), -1, np.int32)
+        clen = np.zeros((B, T), np.int32)
+        for b, (tid, arrs) in enumerate(toks):
+            ids[b, :len(tid)] = tid
+            mask[b, :len(tid)] = 1
+            for i, a in enumerate(arrs):
+                if len(a) > 1:
+                    cand[b, i, :len(a)] = [self.polyphone2id[p] for p in a]
+                    clen[b, i] = len(a)
+        choice, pros = self.model.decide(ids, mask, cand, clen)
+        return [self._phonemes(arrs, choice[b].tolist(), pros[b].tolist()) for b, (_, arrs) in enumerate(toks)]
+
+
+class Model:
+    """cli/model.py's Model on existing parts: `backend_session` an InferenceSession (session.py) of the acoustic model,
+    `phone_table` / `speaker_table` dicts or `symbol id` files, `frontend` a Frontend.  No hub download."""
+
+    def __init__(self, backend_session, phone_table, speaker_table, frontend):
+        self.frontend = frontend
+        self.session = backend_session
+        self.phone2id = self.read_table(phone_table) if isinstance(phone_table, (str, os.PathLike)) else dict(phone_table)
+        self.speaker2id = self.read_table(speaker_table) if isinstance(speaker_table, (str, os.PathLike)) \
+            else dict(speaker_table)
+
+    def read_table(self, fname):
+        table = {}
+        with open(fname, encoding="utf-8") as fin:
+            for line in fin:
+                arr = line.split()
+                assert len(arr) == 2
+                table[arr[0]] = int(arr[1])
+        return table
+
+    def synthesis(self, text, speaker="default"):
+        """cli/model.py:43-61 -> (phonemes, int16 audio)."""
+        phonemes = self.frontend.compute(text)
+        phonemes_id = [self.phone2id[x] for x in phonemes]
+        scales = [0.667, 1.0, 0.8]
+        sid = self.speaker2id.get(speaker, 0)
+        outputs = self.session.run(None, {
+            "input": np.expand_dims(np.array(phonemes_id), axis=0),
+            "input_lengths": np.array([len(phonemes)]),
+            "scales": np.expand_dims(np.array(scales, dtype=np.float32), axis=0),
+            "sid": np.array([sid]),
+        })
+        audio = outputs[0][0][0]
+        audio = (audio * 32767).astype(np.int16)
+        return phonemes, audio

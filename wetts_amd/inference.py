@@ -32,7 +32,10 @@ def get_args(argv=None):
     parser.add_argument("--outdir", required=True, help="ouput directory")
     parser.add_argument("--phone_table", required=True, help="input phone dict")
     parser.add_argument("--speaker_table", default=True, help="speaker table")
-    parser.add_argument("--test_file", required=True, help="test file")
+    parser.add_argument("--test_file", default=None, help="test file")
+    parser.add_argument("--front_dir", default=None, help="frontend directory (with --text_file)")
+    parser.add_argument("--text_file", default=None, help="`utt_id text` lines, synthesised from text (needs --front_dir)")
+    parser.add_argument("--speaker", default="default", help="speaker of every --text_file line")
     parser.add_argument("--gpu", type=int, default=0, help="gpu id for this local rank")
     parser.add_argument("--batch", type=int, default=1,
                         help="largest padded sub-batch per infer() call (1 = the reference's loop)")
@@ -42,7 +45,12 @@ def get_args(argv=None):
                         help="with --batch > 1: decode every utterance over its own frames (ragged; auto = when "
                              "the model supports it) or the whole padded sub-batch like infer() (padded)")
     parser.add_argument("--seed", type=int, default=None, help="seed for the sampling noise")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if (args.front_dir is None) != (args.text_file is None):
+        parser.error("--front_dir and --text_file go together")
+    if (args.test_file is None) == (args.text_file is None):
+        parser.error("exactly one of --test_file and --text_file is required")
+    return args
 
 
 def read_table(path):
@@ -79,10 +87,19 @@ def main(argv=None):
     net_g = build_model(args, phone_dict, speaker_dict, hps)
     if args.seed is not None:
         torch.manual_seed(args.seed)
-    lines = [l.strip().split("|") for l in open(args.test_file) if l.strip()]
+    if args.text_file is not None:
+        from .frontend import Frontend
+        front = Frontend(args.front_dir, device=torch.device("cuda", args.gpu))
+        utts = [l.strip().split(None, 1) for l in open(args.text_file, encoding="utf-8") if l.strip()]
+        assert all(len(u) == 2 for u in utts), "--text_file lines are `utt_id text`"
+        phones = front.compute_batch([text.strip() for _, text in utts])
+        lines = [(utt + ".wav", args.speaker, " ".join(ph)) for (utt, _), ph in zip(utts, phones)]
+        sids = [speaker_dict.get(args.speaker, 0)] * len(lines)
+    else:
+        lines = [l.strip().split("|") for l in open(args.test_file) if l.strip()]
+        sids = [speaker_dict[spk] for (_, spk, _) in lines]
     sr = hps.data.sampling_rate
     seqs = [[phone_dict[s] for s in text.split()] for (_, _, text) in lines]  # KeyError like the reference
-    sids = [speaker_dict[spk] for (_, spk, _) in lines]
     ragged = False
     if args.batch <= 1:
         # the reference's loop: one utterance per infer() call (inference.py:83-110)

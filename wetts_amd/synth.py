@@ -236,6 +236,51 @@ def make_duration_discriminator_state_dict(version, seed=0, in_channels=192, fil
     return sd
 
 
+def make_frontend_state_dict(cfg, seed=0):
+    """Reference-keyed state_dict of the frontend (frontend/model.py:21-73) as frontend/train.py:215 saves it, for a
+    frontend config dict (wetts_frontend_config_t's fields), deterministic in `seed` from a generator of its own; plain
+    torch, no `transformers`.  Embeddings randn (their sum is normalised at once), Linear weights randn * fan_in ** -0.5,
+    biases 0.05 * randn, LayerNorm weights 1 + 0.1 * randn and biases 0.1 * randn: every LayerNorm output has unit scale,
+    so both classifiers' logits are O(1) and the probabilities stay away from 0 and 1.  Carries bert.pooler.* and
+    bert.embeddings.position_ids, which the model constructs and the frontend never reads."""
+    g = torch.Generator().manual_seed(int(seed))
+    d = int(cfg["hidden_size"])
+    sd = {}
+
+    def lin(name, out, inp):
+        sd[name + ".weight"] = torch.randn(out, inp, generator=g, dtype=torch.float32) * float(inp) ** -0.5
+        sd[name + ".bias"] = 0.05 * torch.randn(out, generator=g, dtype=torch.float32)
+
+    def norm(name):
+        sd[name + ".weight"] = 1.0 + 0.1 * torch.randn(d, generator=g, dtype=torch.float32)
+        sd[name + ".bias"] = 0.1 * torch.randn(d, generator=g, dtype=torch.float32)
+
+    for name, rows in (("word", "vocab_size"), ("position", "max_position_embeddings"), ("token_type", "type_vocab_size")):
+        sd[f"bert.embeddings.{name}_embeddings.weight"] = torch.randn(int(cfg[rows]), d, generator=g, dtype=torch.float32)
+    sd["bert.embeddings.position_ids"] = torch.arange(int(cfg["max_position_embeddings"])).unsqueeze(0)
+    norm("bert.embeddings.LayerNorm")
+    for i in range(int(cfg["num_layers"])):
+        p = f"bert.encoder.layer.{i}."
+        for n in ("query", "key", "value"):
+            lin(p + "attention.self." + n, d, d)
+        lin(p + "attention.output.dense", d, d)
+        norm(p + "attention.output.LayerNorm")
+        lin(p + "intermediate.dense", int(cfg["intermediate_size"]), d)
+        lin(p + "output.dense", d, int(cfg["intermediate_size"]))
+        norm(p + "output.LayerNorm")
+    lin("bert.pooler.dense", d, d)
+    sd["transform.self_attn.in_proj_weight"] = torch.randn(3 * d, d, generator=g, dtype=torch.float32) * float(d) ** -0.5
+    sd["transform.self_attn.in_proj_bias"] = 0.05 * torch.randn(3 * d, generator=g, dtype=torch.float32)
+    lin("transform.self_attn.out_proj", d, d)
+    lin("transform.linear1", int(cfg["transform_ff"]), d)
+    lin("transform.linear2", d, int(cfg["transform_ff"]))
+    norm("transform.norm1")
+    norm("transform.norm2")
+    lin("phone_classifier", int(cfg["num_polyphones"]), d)
+    lin("prosody_classifier", int(cfg["num_prosody"]), d)
+    return sd
+
+
 def blob_checksum(blob):
     """Order-sensitive fingerprint of a float32 blob (guards golden fixtures against RNG drift)."""
     b = blob.detach().to(torch.float64)
