@@ -832,6 +832,56 @@ int32_t wetts_frontend_decide(const float* phone_prob, const float* prosody_prob
                               const int32_t* cand_len, int32_t N, int32_t P, int32_t R, int32_t max_cand, int32_t* choice,
                               int32_t* prosody, void* stream);
 
+/* ---- The 16-bit conv launches, one at a time (csrc/conv16_entry.hip) -----------------------------------------------
+ *
+ * Each entry runs ONE launch of the 16-bit decoder / flow (conv_bf16.hip, resblock16.hip, resblock2_stage16.hip,
+ * wn16.hip) on caller data, with the launch code wetts_hifigan and the 16-bit WaveNet use.  Weights arrive as f32 in
+ * the reference's shapes ([Cout][Cin][k]; transposed [Cin][Cout][k]) and are packed here; activations arrive and
+ * leave as the kernels' own 16-bit CHANNEL-LAST tensors [B][T][C] (bfloat16, or IEEE half with f16 != 0); bias /
+ * bias_b / mask / skip / conv_post's output are f32.  Every entry allocates what it packs, synchronises `stream` and
+ * frees it before it returns; shapes the launchers refuse give WETTS_E_INVALID.  Test and measurement entries: the
+ * product path never calls them. */
+#define WETTS_CONV16_F16 1        /* IEEE half storage (else bfloat16)                                   */
+#define WETTS_CONV16_TRANSPOSED 2 /* ConvTranspose1d at rate `up` (polyphase); no residual / accumulate  */
+#define WETTS_CONV16_LRELU 4      /* leaky-relu(in_slope) on the input, rounded to 16 bit                */
+#define WETTS_CONV16_ACCUM 8      /* add the previous contents of `out` (the running MRF sum)            */
+#define WETTS_CONV16_BASIC 16     /* ConvBParams::basic                                                  */
+#define WETTS_CONV16_TAG 32       /* ConvBParams::tag (the MRF launches' own kernel symbol)              */
+/* out [B][Tout][Cout] = (conv(act(x)) + bias + bias_b[b] + res [+ out]) / out_div, rounded once.  x [B][Tin][Cin];
+ * Tout = Tin + 2 padding - (k - 1) dilation, transposed (Tin - 1) up - 2 padding + k; bias [Cout], bias_b [B][Cout] and
+ * res [B][Tout][Cout] may be NULL. */
+int32_t wetts_conv16(const float* w, const float* bias, const float* bias_b, const void* x, const void* res, void* out,
+                     int32_t B, int32_t Cin, int32_t Cout, int32_t k, int32_t dilation, int32_t padding, int32_t up,
+                     int32_t Tin, int32_t Tout, int32_t flags, float in_slope, float out_div, void* stream);
+/* The WaveNet in_layer with the gate in its epilogue (epi_mode 1): w [2H][H][k], 'same' padding;
+ * acts [B][T][H] = tanh(a) * sigmoid(b) of the rounded conv outputs (+ bias [2H], + bias_b [B][bias_b_stride]). */
+int32_t wetts_conv16_wn_gate(const float* w, const float* bias, const float* bias_b, int64_t bias_b_stride, const void* x,
+                             void* acts, int32_t B, int32_t H, int32_t k, int32_t dilation, int32_t T, int32_t f16,
+                             void* stream);
+/* The WaveNet res_skip 1x1 conv with the update in its epilogue (epi_mode 2): w [last ? H : 2H][H][1];
+ * h [B][T][H] (16 bit) = (h + rs[:H]) * mask in place unless `last`; skip [B][T][H] f32 (+)= rs[H:] (= when `first`). */
+int32_t wetts_conv16_wn_update(const float* w, const float* bias, const void* acts, void* h, float* skip,
+                               const float* mask, int32_t B, int32_t H, int32_t T, int32_t last, int32_t first,
+                               int32_t f16, void* stream);
+/* The two stand-alone WaveNet kernels: xin [rows][2H] -> acts [rows][H]; rs [rows][last ? H : 2H] -> h, skip. */
+int32_t wetts_wn16_gate(const void* xin, void* acts, int64_t rows, int32_t H, int32_t f16, void* stream);
+int32_t wetts_wn16_update(const void* rs, void* h, float* skip, const float* mask, int32_t last, int32_t first,
+                          int64_t rows, int32_t H, int32_t f16, void* stream);
+/* conv_post: out [B][T] f32 = tanh(conv(lrelu_0.01(x), w [1][C][7])).  mfma != 0: k_conv_post_mfma16 (C == 32, the
+ * weight padded to 32 rows and packed, epi_mode 3); 0: k_conv_post_bf16 (f32 weights). */
+int32_t wetts_conv16_post(const float* w, const void* x, float* out, int32_t B, int32_t C, int32_t T, int32_t mfma,
+                          int32_t f16, void* stream);
+/* One ResBlock launch.  form 0: a ResBlock1 pair  out = (x + c2(lrelu(c1(lrelu(x)))) [+ out]) / out_div  (c2 at
+ * dilation 1, nchain 1); 1: a ResBlock2 chain  t = x + c1(lrelu(x)), out = (t + c2(lrelu(t)) [+ out]) / out_div
+ * (nchain 1); 2: a ResBlock2 stage, the sum of nchain <= 3 chains over out_div (accum must be 0).  w1 / b1 / w2 / b2:
+ * nchain device pointers each ([C][C][k] and [C]); ktaps / dil1 / dil2: nchain host ints.  fused != 0 runs the fused
+ * launcher; 0 runs the same arithmetic conv by conv through launch_conv_bf16 and leaves the intermediate (ft / t) of
+ * chain j in mid [nchain][B][T][C] (mid is not touched when fused and may then be NULL). */
+int32_t wetts_resblock16(int32_t form, int32_t fused, int32_t nchain, const float* const* w1, const float* const* b1,
+                         const float* const* w2, const float* const* b2, const int32_t* ktaps, const int32_t* dil1,
+                         const int32_t* dil2, const void* x, void* out, void* mid, int32_t B, int32_t C, int32_t T,
+                         int32_t accum, float out_div, int32_t f16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

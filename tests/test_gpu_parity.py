@@ -194,7 +194,9 @@ def test_product_path_fails_loudly_without_device_weights():
 
 @pytest.mark.parametrize("name", ["v1_b2", "v3_b2"])
 def test_hifigan_f16_mode_matches_its_numerics_spec(name):
-    """IEEE-half decoder (configs[4] precision): 11-bit mantissa => ~8x tighter than bf16."""
+    """IEEE-half decoder (configs[4] precision): 11-bit mantissa => ~8x tighter than bf16.
+    What this still covers: the COMPOSITION of the launches and its rounding points.  Locality -- every single
+    launch against float64, element by element, at the tile remainders -- is pinned in tests/test_gpu_conv16.py."""
     from oracle import vits_oracle as vo
     case = util.load_case(name)
     net, cfg, W = _model(case)
@@ -216,7 +218,9 @@ def test_hifigan_f16_mode_matches_its_numerics_spec(name):
 def test_hifigan_bf16_mode_matches_its_numerics_spec(name):
     """bf16 decoder (configs[2]/[4] precision): against oracle.hifigan_bf16sim (same rounding
     points) and, loosely, against the f32 oracle.  Tolerances: rel RMS 1e-2 vs the bf16 spec
-    (f32-accumulation order can flip an occasional bf16 rounding), 6e-2 vs f32."""
+    (f32-accumulation order can flip an occasional bf16 rounding), 6e-2 vs f32.
+    What this still covers: the COMPOSITION of the launches and its rounding points.  Locality -- every single
+    launch against float64, element by element, at the tile remainders -- is pinned in tests/test_gpu_conv16.py."""
     from oracle import vits_oracle as vo
     case = util.load_case(name)
     net, cfg, W = _model(case)
@@ -247,7 +251,9 @@ def test_fused_resblock_pair_bit_identical(dtype, L, cname):
     chains and resblock2_stage16.hip whole stages at 16 bit) perform the
     arithmetic of two conv launches in the same order with the same rounding points: outputs must
     be EQUAL, including at tile seams
-    (L*hop spans several time tiles), sequence ends (zero padding of c2's input) and L=1."""
+    (L*hop spans several time tiles), sequence ends (zero padding of c2's input) and L=1.
+    Both sides of the 16-bit comparison share conv16_dev.h: tests/test_gpu_conv16.py holds each side to float64 and
+    repeats the equality per launch at lengths chosen for the seams."""
     # v1: ResBlock1 pairs; v3: ResBlock2 chains (RB2 instantiations), one launch per chain -- or, ":stage", one launch
     # per STAGE at 16 bit (resblock2_stage16.hip: all chains of a stage, the running sum in registers)
     cname, _, variant = cname.partition(":")
@@ -411,7 +417,9 @@ def test_flow_16bit_mode_matches_its_numerics_spec(name, dtype):
     """16-bit WaveNet layers of the flow (wetts_set_flow_precision; BASELINE configs[2] precision for
     the part of the step that dominates at B = 64): against oracle.wn_16bit_sim (same rounding
     points, f32 accumulation) and, loosely, against the reference's f32 z.  The alignment (duration
-    path) must not move at all; switching back restores the exact-f32 flow."""
+    path) must not move at all; switching back restores the exact-f32 flow.
+    What this still covers: the COMPOSITION of the launches and its rounding points.  Locality -- every single
+    launch against float64, element by element, at the tile remainders -- is pinned in tests/test_gpu_conv16.py."""
     from oracle import vits_oracle as vo
     case = util.load_case(name)
     net, cfg, W = _model(case)

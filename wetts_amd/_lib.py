@@ -220,7 +220,20 @@ SIGNATURES = {
     "wetts_frontend_heads": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     "wetts_frontend_layer": (_I32, [_P, _I32, _P, _P, _I32, _I32, _P, _P]),
     "wetts_frontend_decide": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "wetts_conv16": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F,
+                            _P]),
+    "wetts_conv16_wn_gate": (_I32, [_P, _P, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "wetts_conv16_wn_update": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "wetts_wn16_gate": (_I32, [_P, _P, _I64, _I32, _I32, _P]),
+    "wetts_wn16_update": (_I32, [_P, _P, _P, _P, _I32, _I32, _I64, _I32, _I32, _P]),
+    "wetts_conv16_post": (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "wetts_resblock16": (_I32, [_I32, _I32, _I32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _P, _P, _P, _I32, _I32, _I32, _I32, _F,
+                                _I32, _P]),
 }
+
+# WETTS_CONV16_* flags of wetts_conv16
+CONV16_F16, CONV16_TRANSPOSED, CONV16_LRELU, CONV16_ACCUM, CONV16_BASIC, CONV16_TAG = 1, 2, 4, 8, 16, 32
 
 # WETTS_STATUS_* bits of include/wetts_hip.h
 STATUS_SPLINE_DOMAIN, STATUS_PHONE_ID_RANGE, STATUS_SPEAKER_ID_RANGE, STATUS_DURATION_NONFINITE = 1, 2, 4, 8
