@@ -58,6 +58,9 @@ extern "C" {
                                            * slice id outside [0, len - segment] (the reference slices out of range) */
 #define WETTS_STATUS_TOKEN_ID_RANGE 128   /* wetts_frontend_*: a token id outside [0, vocab_size) (nn.Embedding IndexError) */
 #define WETTS_STATUS_TYPE_ID_RANGE 256    /* wetts_frontend_*: a token type id outside [0, type_vocab_size) */
+#define WETTS_STATUS_LABEL_RANGE 512      /* wetts_frontend_score*: a label that is neither -100 nor a class (torch's
+                                             `IndexError: Target .. is out of bounds` in F.cross_entropy) */
+#define WETTS_STATUS_LABEL_AT_PAD 1024    /* wetts_frontend_score*: a label other than -100 at a token whose mask is 0 */
 
 #define WETTS_MAX_STAGES 8
 #define WETTS_MAX_RB_KERNELS 8
@@ -831,6 +834,42 @@ int32_t wetts_frontend_layer(const wetts_frontend_t* f, int32_t layer, float* x,
 int32_t wetts_frontend_decide(const float* phone_prob, const float* prosody_prob, const int32_t* cand,
                               const int32_t* cand_len, int32_t N, int32_t P, int32_t R, int32_t max_cand, int32_t* choice,
                               int32_t* prosody, void* stream);
+
+/* ---- scoring the text frontend (csrc/frontend_score.hip) ------------------------------------------------------------
+ * The validation pass of frontend/train.py:43-94 (two F.cross_entropy(.., ignore_index=-100) terms, compute_accuracy),
+ * the masked accuracy counts of frontend/test_polyphone.py:72-86 and the counts behind the three binary F1 scores of
+ * frontend/test_prosody.py:77-102, from the eval-mode forward pass, without a logit in memory: the classifier GEMM
+ * leaves one 16-byte record {maximum, sum of exp, lowest argmax, label's logit} per (tile of 32 classes, token), a
+ * second launch combines a token's records, a third (one block, float64 sums in a fixed order, no float atomics)
+ * reduces.  phone_labels, prosody_labels: int64 [B][T], -100 = ignored (dataset.py:19); either may be NULL = all
+ * ignored.  Outputs, all on the device:
+ *   nll_phone, nll_prosody [B][T] f32: (max + log sum exp(z - max)) - z[label]; 0 where the label is ignored
+ *   pred_phone, pred_prosody [B][T] int32: the LOWEST class of the largest logit; -1 where attention_mask is 0
+ *     (these four may be NULL)
+ *   losses f32[2]: the mean nll over the scored labels of each head; NaN for a head without any (torch's 0 / 0)
+ *   counts int64[22]: [0] phone labels scored, [1] of them predicted; [2], [3] the same for the prosody head;
+ *     [4..12] TP, FP, FN of `x > 0`, then of `x > 1`, then of `x > 2`, over the positions 1 .. len_b of every row b,
+ *     len_b = the row's count of prosody labels != -100, the slice clipped to T (test_prosody.py:91-93; a -100 label
+ *     inside it counts as 0, as does the -1 prediction of a padded token); [13..21] the same nine over 1 .. len_b - 1
+ *     (--exclude_end, test_prosody.py:88-89).  Counts, not scores: they add across batches.
+ * A label outside [0, classes) that is not -100 ORs WETTS_STATUS_LABEL_RANGE into *status (device int32, may be NULL),
+ * a label other than -100 at a token whose mask is 0 WETTS_STATUS_LABEL_AT_PAD (the reference computes on padding,
+ * this project zeroes it: there is no common answer); neither token is scored.  Token / type ids: as _forward.
+ * `workspace`: 16-byte aligned, workspace_bytes >= wetts_frontend_score_workspace_bytes(f, B, T).  Allocates nothing,
+ * no host synchronisation. */
+int64_t wetts_frontend_score_workspace_bytes(const wetts_frontend_t* f, int32_t B, int32_t T);
+int32_t wetts_frontend_score(const wetts_frontend_t* f, const int64_t* input_ids, const int64_t* token_type_ids,
+                             const int64_t* attention_mask, const int64_t* phone_labels, const int64_t* prosody_labels,
+                             int32_t B, int32_t T, float* nll_phone, float* nll_prosody, int32_t* pred_phone,
+                             int32_t* pred_prosody, float* losses, int64_t* counts, void* workspace,
+                             int64_t workspace_bytes, int32_t* status, void* stream);
+/* The stage: the three scoring launches on given x [B * T][hidden] and key_mask [B * T] (1.0 / 0.0), the counterpart of
+ * wetts_frontend_heads.  The same workspace size serves (it uses the scoring part only). */
+int32_t wetts_frontend_score_heads(const wetts_frontend_t* f, const float* x, const float* key_mask,
+                                   const int64_t* phone_labels, const int64_t* prosody_labels, int32_t B, int32_t T,
+                                   float* nll_phone, float* nll_prosody, int32_t* pred_phone, int32_t* pred_prosody,
+                                   float* losses, int64_t* counts, void* workspace, int64_t workspace_bytes,
+                                   int32_t* status, void* stream);
 
 /* ---- The 16-bit conv launches, one at a time (csrc/conv16_entry.hip) -----------------------------------------------
  *

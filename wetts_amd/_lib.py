@@ -220,6 +220,9 @@ SIGNATURES = {
     "wetts_frontend_heads": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     "wetts_frontend_layer": (_I32, [_P, _I32, _P, _P, _I32, _I32, _P, _P]),
     "wetts_frontend_decide": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "wetts_frontend_score_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_frontend_score": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "wetts_frontend_score_heads": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "wetts_conv16": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F,
                             _P]),
     "wetts_conv16_wn_gate": (_I32, [_P, _P, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
@@ -239,6 +242,7 @@ CONV16_F16, CONV16_TRANSPOSED, CONV16_LRELU, CONV16_ACCUM, CONV16_BASIC, CONV16_
 STATUS_SPLINE_DOMAIN, STATUS_PHONE_ID_RANGE, STATUS_SPEAKER_ID_RANGE, STATUS_DURATION_NONFINITE = 1, 2, 4, 8
 STATUS_ALIGN_TEXT_LONGER, STATUS_DURATION_NEGATIVE, STATUS_SEGMENT_LONGER = 16, 32, 64
 STATUS_TOKEN_ID_RANGE, STATUS_TYPE_ID_RANGE = 128, 256
+STATUS_LABEL_RANGE, STATUS_LABEL_AT_PAD = 512, 1024
 
 _lib = None
 

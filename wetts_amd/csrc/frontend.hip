@@ -11,33 +11,17 @@
 // fixed by the block shape, a LayerNorm / classifier / softmax row is reduced by one wave in a fixed order, and attention
 // gives a masked key the weight +0 exactly, which changes no bit of a sum.  A row alone and the same row inside a padded
 // batch give the same bits.  No atomics on floats (the status word is an integer OR).
-#include "common.h"
+#include "frontend_dev.h"
 
 #include <math.h>
 
-#include <vector>
-
 namespace wetts {
-
-typedef float f32x16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float fe_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ float fe_wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over the channels of a token, one wave per token, the row in registers (C <= 1024, C % 4 == 0): lane l holds
 // the float4s l, l + 64, ..; two passes (mean, then centred squares), each a per-lane sum in ascending order and the
 // butterfly over the lanes.  Biased variance, as F.layer_norm.
-constexpr int kFeMaxC = 1024, kFeRowV = kFeMaxC / 256;
+constexpr int kFeRowV = kFeMaxC / 256;
 
 __device__ __forceinline__ void fe_layer_norm_row(float4 v[kFeRowV], int C, const float* __restrict__ gamma,
                                                   const float* __restrict__ beta, float eps, float* __restrict__ out,
@@ -136,7 +120,6 @@ fe_add_ln_kernel(const float* x, const float* res, const float* __restrict__ gam
 // column is fixed by K alone, so a token's result does not depend on N or on its neighbours.
 // M % 4 == 0 and K % 8 == 0 (the launcher checks); rows / columns past M / N are read clamped and not stored.
 enum { FE_EPI_BIAS = 0, FE_EPI_GELU = 1, FE_EPI_RELU = 2, FE_EPI_RES = 3 };
-constexpr int kFeKG = 8, kFeRing = 4, kFeNT = 64;
 
 template <int EPI>
 __global__ void __launch_bounds__(64 * kFeKG)
@@ -240,7 +223,7 @@ fe_linear_kernel(const float* __restrict__ X, const float* __restrict__ W, const
 // order, then the butterfly); (2) lane d (and d + 64) adds p[key] * v[key][d] over the keys in ascending order, and the
 // quotient by the sum is stored.  A masked key adds +0 to every sum, so a row's bits do not depend on the padding behind
 // it.  A query without any valid key gives zeros (the reference gives NaN there; no other row reads it).
-constexpr int kFeMaxT = 512, kFeMaxDk = 96, kFeQW = 4;
+constexpr int kFeQW = 4;
 
 __global__ void __launch_bounds__(256)
 fe_attention_kernel(const float* __restrict__ qkv, const float* __restrict__ maskf, float* __restrict__ ctx, int T, int H,
@@ -560,24 +543,6 @@ static FeLayout fe_layout(const wetts_frontend_config_t* c) {
   return l;
 }
 
-struct FeBlock {  // one post-norm transformer layer
-  const float *wqkv, *bqkv, *wo, *bo, *g1, *b1, *w1, *bb1, *w2, *bb2, *g2, *b2;
-  int heads, ff, act;
-  float eps;
-};
-
-}  // namespace wetts
-
-struct wetts_frontend {
-  wetts_frontend_config_t cfg;
-  float* blob = nullptr;
-  const float *word = nullptr, *pos = nullptr, *type = nullptr, *eg = nullptr, *eb = nullptr;
-  std::vector<wetts::FeBlock> blocks;  // the BERT layers, then `transform`
-  const float *wp = nullptr, *bp = nullptr, *wr = nullptr, *br = nullptr;
-};
-
-namespace wetts {
-
 static int32_t fe_launch_linear(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int K,
                                 int M, int epi, hipStream_t s) {
   WETTS_REQUIRE(x && w && bias && y && N >= 1, "frontend linear: bad argument (N=%d)", N);
@@ -661,6 +626,29 @@ static int32_t fe_run_block(const FeBlock& k, int d, float* h, float* h2, float*
   WETTS_TRY(fe_launch_linear(h, k.w1, k.bb1, nullptr, ff, N, d, k.ff, k.act, s));
   WETTS_TRY(fe_launch_linear(ff, k.w2, k.bb2, h, h2, N, k.ff, d, FE_EPI_RES, s));
   return fe_launch_add_ln(h2, nullptr, k.g2, k.b2, k.eps, N, d, h, s);
+}
+
+int64_t fe_workspace_floats(const wetts_frontend* h, int B, int T) {
+  int64_t off[7];
+  fe_regions(h->cfg, B, T, off);
+  return off[6];
+}
+
+int32_t fe_hidden(const wetts_frontend* h, const int64_t* ids, const int64_t* tts, const int64_t* mask, int B, int T,
+                  void* workspace, int32_t* status, hipStream_t s, const char* what, const float** x, const float** maskf) {
+  WETTS_REQUIRE(B >= 1 && T >= 1, "%s: B=%d and T=%d must be at least 1", what, B, T);
+  WETTS_REQUIRE(T <= h->cfg.max_position_embeddings && T <= kFeMaxT, "%s: T=%d exceeds the %d positions", what, T,
+                h->cfg.max_position_embeddings < kFeMaxT ? h->cfg.max_position_embeddings : kFeMaxT);
+  WETTS_REQUIRE((int64_t)B * T <= 0x7fffffff / 4, "%s: %d x %d tokens exceed one call", what, B, T);
+  int64_t off[7];
+  fe_regions(h->cfg, B, T, off);
+  float* ws = (float*)workspace;
+  float *hb = ws + off[0], *h2 = ws + off[1], *ctx = ws + off[2], *qkv = ws + off[3], *ff = ws + off[4], *mf = ws + off[5];
+  WETTS_TRY(fe_launch_embed(h, ids, tts, mask, B, T, hb, mf, status, s));
+  for (const FeBlock& k : h->blocks) WETTS_TRY(fe_run_block(k, h->cfg.hidden_size, hb, h2, ctx, qkv, ff, mf, B, T, s));
+  *x = hb;
+  *maskf = mf;
+  return WETTS_OK;
 }
 
 }  // namespace wetts
@@ -794,17 +782,9 @@ int32_t wetts_frontend_forward(const wetts_frontend_t* h, const int64_t* input_i
                                const int64_t* attention_mask, int32_t B, int32_t T, int32_t softmax, float* phone_out,
                                float* prosody_out, void* workspace, int32_t* status, void* stream) {
   WETTS_REQUIRE(h && input_ids && phone_out && prosody_out && workspace, "null argument");
-  WETTS_REQUIRE(B >= 1 && T >= 1, "frontend_forward: B=%d and T=%d must be at least 1", B, T);
-  WETTS_REQUIRE(T <= h->cfg.max_position_embeddings && T <= kFeMaxT, "frontend_forward: T=%d exceeds the %d positions", T,
-                h->cfg.max_position_embeddings < kFeMaxT ? h->cfg.max_position_embeddings : kFeMaxT);
-  WETTS_REQUIRE((int64_t)B * T <= 0x7fffffff / 4, "frontend_forward: %d x %d tokens exceed one call", B, T);
-  int64_t off[7];
-  fe_regions(h->cfg, B, T, off);
-  float* ws = (float*)workspace;
-  float *hb = ws + off[0], *h2 = ws + off[1], *ctx = ws + off[2], *qkv = ws + off[3], *ff = ws + off[4], *maskf = ws + off[5];
   hipStream_t s = (hipStream_t)stream;
-  WETTS_TRY(fe_launch_embed(h, input_ids, token_type_ids, attention_mask, B, T, hb, maskf, status, s));
-  for (const FeBlock& k : h->blocks) WETTS_TRY(fe_run_block(k, h->cfg.hidden_size, hb, h2, ctx, qkv, ff, maskf, B, T, s));
+  const float *hb, *maskf;
+  WETTS_TRY(fe_hidden(h, input_ids, token_type_ids, attention_mask, B, T, workspace, status, s, "frontend_forward", &hb, &maskf));
   return fe_launch_heads(h, hb, maskf, B * T, softmax, phone_out, prosody_out, s);
 }
 

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, checkpoint
+from .frontend_data import IGNORE_ID  # noqa: F401  (-100, frontend/dataset.py:19)
 
 # frontend/model.py:33-42: substring of bert_name_or_path -> (d_model, nhead, dim_feedforward) of `transform`
 TRANSFORM_SHAPES = (("bert-chinese-base", (768, 8, 2048)), ("TinyBERT_4L_zh_backup", (312, 12, 1200)))
@@ -245,6 +246,132 @@ class FrontendModel:
         host = out.cpu().numpy()
         self._raise_status(int(host[-1]))
         return host[:B * T].reshape(B, T), host[B * T:2 * B * T].reshape(B, T)
+
+    def _labels(self, labels, name, B, T):
+        if labels is None:
+            return None
+        labels = torch.as_tensor(labels)
+        if tuple(labels.shape) != (B, T) or labels.is_floating_point() or labels.dtype == torch.bool:
+            raise ValueError(f"{name} must be an integer [{B}, {T}] tensor, got {labels.dtype} {tuple(labels.shape)}")
+        return labels.to(device=self._device, dtype=torch.int64).contiguous()
+
+    def score(self, inputs, phone_labels=None, prosody_labels=None, *, polyphone_weight=0.5):
+        """The validation pass of frontend/train.py:63-84 and the counts of test_polyphone.py:76-82 and
+        test_prosody.py:81-100 in one call on the device, without logits: `inputs` as forward() takes it, labels int
+        [B, T] with IGNORE_ID = -100 (None: all ignored) -> FrontendScores of device tensors.  No read-back here; the
+        status word (a label outside its classes, a label at a padded token) is raised by FrontendScores.host()."""
+        ids, tt, mask = self._inputs(inputs["input_ids"], inputs.get("token_type_ids"), inputs.get("attention_mask"))
+        B, T = ids.shape
+        pl, rl = self._labels(phone_labels, "phone_labels", B, T), self._labels(prosody_labels, "prosody_labels", B, T)
+        w = float(polyphone_weight)
+        lib = _lib.load()
+        nbytes = int(lib.wetts_frontend_score_workspace_bytes(self._handle, B, T))
+        if nbytes < 0:
+            raise _lib.WettsError(f"frontend_score_workspace_bytes: {_lib.last_error()}")
+        with torch.cuda.device(self._device):
+            ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self._device)
+            nll = torch.empty(2, B, T, dtype=torch.float32, device=self._device)
+            pred = torch.empty(2, B, T, dtype=torch.int32, device=self._device)
+            losses = torch.empty(2, dtype=torch.float32, device=self._device)
+            counts = torch.empty(22, dtype=torch.int64, device=self._device)
+            status = torch.zeros(1, dtype=torch.int32, device=self._device)
+            _lib.check(lib.wetts_frontend_score(self._handle, _lib.ptr(ids), _lib.ptr(tt), _lib.ptr(mask), _lib.ptr(pl),
+                                                _lib.ptr(rl), B, T, _lib.ptr(nll[0]), _lib.ptr(nll[1]), _lib.ptr(pred[0]),
+                                                _lib.ptr(pred[1]), _lib.ptr(losses), _lib.ptr(counts), _lib.ptr(ws), nbytes,
+                                                _lib.ptr(status), _lib.current_stream_ptr()), "frontend_score")
+        return FrontendScores(losses, counts, nll, pred, status, w)
+
+
+def compute_accuracy(counts, head):
+    """train.py:31-40 on accumulated counts (a sequence of 22 numbers, or FrontendScores.counts read back):
+    correct / total of `head` ("phone" / "polyphone" or "prosody"); NaN for a head without labels."""
+    if head not in ("phone", "polyphone", "prosody"):
+        raise ValueError(f"head must be 'phone', 'polyphone' or 'prosody', got {head!r}")
+    o = 2 if head == "prosody" else 0
+    total, correct = int(counts[o]), int(counts[o + 1])
+    return float(correct) / float(total) if total > 0 else float("nan")
+
+
+def prosody_f1(counts, exclude_end=False):
+    """test_prosody.py:95-100 on accumulated counts -> (pw, pph, iph) f1 scores, 2 TP / (2 TP + FP + FN); an empty
+    denominator gives 0.0, which is what sklearn.metrics.f1_score returns there."""
+    if len(counts) != 22:
+        raise ValueError(f"counts must hold 22 numbers, got {len(counts)}")
+    o = 13 if exclude_end else 4
+    out = []
+    for th in range(3):
+        tp, fp, fn = (int(counts[o + 3 * th + i]) for i in range(3))
+        den = 2 * tp + fp + fn
+        out.append(2 * tp / den if den else 0.0)
+    return tuple(out)
+
+
+class FrontendScores:
+    """What FrontendModel.score() returns, all on the device: phone_loss, prosody_loss, loss (0-dim f32; NaN for a head
+    without labels, and then for `loss`, as in the reference), counts int64 [22] (include/wetts_hip.h), and per token
+    nll_phone, nll_prosody f32 [B, T] (0 where the label is ignored), pred_phone, pred_prosody int32 [B, T] (-1 at a
+    padded token).  host() reads everything it reports back in ONE copy."""
+
+    def __init__(self, losses, counts, nll, pred, status, polyphone_weight):
+        self.phone_loss, self.prosody_loss = losses[0], losses[1]
+        self.polyphone_weight = polyphone_weight
+        self.counts = counts
+        self.nll_phone, self.nll_prosody = nll[0], nll[1]
+        self.pred_phone, self.pred_prosody = pred[0], pred[1]
+        self._losses, self._status = losses, status
+
+    @property
+    def loss(self):
+        """train.py:83-84 on the two device scalars, in f32 as the reference forms it.  Formed when asked for: like
+        packed(), bookkeeping on a handful of numbers AFTER the kernels (as decide() appends its status word), not
+        arithmetic on activations."""
+        w = self.polyphone_weight
+        return w * self.phone_loss + (1 - w) * self.prosody_loss
+
+    def packed(self):
+        """The int64 device vector host() reads back: the 22 counts, the bits of the two f32 losses, the status word
+        (a 25-element copy after the kernels, as decide() packs its status word: no arithmetic)."""
+        return torch.cat([self.counts, self._losses.view(torch.int32).to(torch.int64), self._status.to(torch.int64)])
+
+    def host(self):
+        """-> HostScores of Python numbers; raises IndexError for a label outside its classes (torch: `Target .. is out
+        of bounds`) and ValueError for a label at a padded token."""
+        return HostScores.from_packed(self.packed().cpu(), self.polyphone_weight)
+
+
+def raise_score_status(bits):
+    """The WETTS_STATUS_* bits of a scoring call as the exceptions torch / this project raise."""
+    if bits & (_lib.STATUS_TOKEN_ID_RANGE | _lib.STATUS_TYPE_ID_RANGE):
+        raise IndexError("index out of range in self: a token or token type id is outside its table")
+    if bits & _lib.STATUS_LABEL_RANGE:
+        raise IndexError("Target is out of bounds: a label is neither IGNORE_ID (-100) nor a class of its head")
+    if bits & _lib.STATUS_LABEL_AT_PAD:
+        raise ValueError("a label other than IGNORE_ID (-100) sits at a token whose attention_mask is 0")
+
+
+class HostScores:
+    """FrontendScores on the host: phone_loss, prosody_loss, loss, phone_acc, prosody_acc (NaN for an empty head, as
+    compute_accuracy returns), num_total / num_correct (the polyphone head's, test_polyphone.py:72-73), counts (a list of
+    22 ints) and f1(exclude_end=False) -> (pw, pph, iph)."""
+
+    @classmethod
+    def from_packed(cls, row, polyphone_weight=0.5):
+        """From one read-back row of FrontendScores.packed(); raises what the status word asks for."""
+        row = torch.as_tensor(row, dtype=torch.int64).cpu()
+        raise_score_status(int(row[24]))
+        pl, rl = row[22:24].to(torch.int32).view(torch.float32).numpy()
+        # train.py:83-84: `1 - w` is formed in double and rounded once, each product and the sum in f32
+        w = float(polyphone_weight)
+        return cls((pl, rl, np.float32(w) * pl + np.float32(1 - w) * rl), row[:22].tolist())
+
+    def __init__(self, losses, counts):
+        self.phone_loss, self.prosody_loss, self.loss = (float(v) for v in losses)
+        self.counts = [int(v) for v in counts]
+        self.phone_acc, self.prosody_acc = compute_accuracy(self.counts, "phone"), compute_accuracy(self.counts, "prosody")
+        self.num_total, self.num_correct = self.counts[0], self.counts[1]
+
+    def f1(self, exclude_end=False):
+        return prosody_f1(self.counts, exclude_end)
 
 
 def load_frontend_model(model_dir, device="cuda"):
