@@ -871,6 +871,102 @@ int32_t wetts_frontend_score_heads(const wetts_frontend_t* f, const float* x, co
                                    float* losses, int64_t* counts, void* workspace, int64_t workspace_bytes,
                                    int32_t* status, void* stream);
 
+/* ---- WavLM, its resampler and the WavLMDiscriminator (losses.py:63-153, model/discriminators.py:452-498;
+ * csrc/wavlm.hip) ------------------------------------------------------------------------------------------------
+ * transformers' WavLMModel in the `wavlm-base` / `wavlm-base-plus` architecture -- feat_extract_norm "group", no conv
+ * bias, post-norm encoder layers, GELU, no attention mask (every row of a batch has the same length) -- without
+ * gradients, f32 throughout, returning every hidden state.  A blob and a handle of its own; the blob holds the
+ * model's parameters under transformers' names, each at a multiple of 4 floats, with three device layouts: the convs
+ * 1 .. of the feature extractor and the positional conv are tap-major, [Cout][k][Cin]; the positional conv has its
+ * weight norm folded; gru_rel_pos_const is [heads].  masked_spec_embed is not part of it.
+ * Limits: conv_dim multiples of 8, the last at most 1024; hidden_size a multiple of 8 up to 1024; heads of at most 96
+ * channels; intermediate_size a multiple of 8; positional groups of a multiple of 4 channels; at most 512 frames per row.
+ * Activations are token-major: [B][T][channels]. */
+#define WETTS_WAVLM_MAX_CONV 8
+typedef struct wetts_wavlm_config {
+  int32_t num_conv_layers;
+  int32_t conv_dim[WETTS_WAVLM_MAX_CONV], conv_kernel[WETTS_WAVLM_MAX_CONV], conv_stride[WETTS_WAVLM_MAX_CONV];
+  int32_t hidden_size, num_layers, num_heads, intermediate_size;
+  int32_t pos_kernel, pos_groups;              /* num_conv_pos_embeddings, num_conv_pos_embedding_groups */
+  int32_t num_buckets, max_bucket_distance;
+  float layer_norm_eps;
+} wetts_wavlm_config_t;
+typedef struct wetts_wavlm wetts_wavlm_t;
+typedef struct wetts_wavlm_disc wetts_wavlm_disc_t;
+
+/* The bucket of a relative position key - query (T5's bidirectional rule as WavLMAttention states it: num_buckets / 2
+ * per sign, exact below num_buckets / 4, then a float32 log ramp truncated to an integer and clamped); -1 on a bad
+ * argument.  Host only.  The handle holds the table of every relative position it can meet. */
+int32_t wetts_wavlm_bucket(int32_t num_buckets, int32_t max_bucket_distance, int32_t relative_position);
+/* Frames the feature extractor leaves of L samples (floor((L - k) / s) + 1 per layer, 0 below one frame); -1 on a bad
+ * config. */
+int64_t wetts_wavlm_num_frames(const wetts_wavlm_config_t* cfg, int64_t L);
+int32_t wetts_wavlm_blob_num_tensors(const wetts_wavlm_config_t* cfg);
+int32_t wetts_wavlm_blob_tensor_info(const wetts_wavlm_config_t* cfg, int32_t index, char* name_buf, size_t name_buf_len,
+                                     int64_t* offset, int64_t* numel, int64_t shape[4]);
+int64_t wetts_wavlm_blob_numel(const wetts_wavlm_config_t* cfg);
+int32_t wetts_wavlm_create(const wetts_wavlm_config_t* cfg, const float* blob_dev, int64_t blob_numel, void* stream,
+                           wetts_wavlm_t** out);
+void wetts_wavlm_destroy(wetts_wavlm_t* w);
+/* Bytes of scratch wetts_wavlm_forward needs for B rows of L samples; negative on a bad argument (L below one frame
+ * and more than 512 frames included). */
+int64_t wetts_wavlm_workspace_bytes(const wetts_wavlm_t* w, int32_t B, int64_t L);
+/* x: B rows of L samples, row b at x + b * x_bs.  hidden [num_layers + 1][B][T][hidden_size], T = the frames of L:
+ * the input of every encoder layer, then the last layer's output.  Every argument is checked before the first launch.
+ * Allocates nothing, no host synchronisation. */
+int32_t wetts_wavlm_forward(const wetts_wavlm_t* w, const float* x, int64_t x_bs, int32_t B, int64_t L, float* hidden,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+/* A stand-in for torchaudio.transforms.Resample at its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff
+ * 0.99), restated from its published arithmetic: orig, new_ the rates over their gcd, width = ceil(6 orig / (0.99
+ * min(orig, new_))), kernel [new_][kernel_stride] the float32 sinc matrix (its 2 width + orig taps, then zeros up to
+ * kernel_stride, a multiple of 8).  `padded` [B][padded_stride] is scratch for the zero-padded signal, padded_stride >=
+ * (L / orig) * orig + kernel_stride.  out [B][(L / orig + 1) * new_]: the frames, interleaved; the caller keeps the
+ * first ceil(new_ L / orig) samples of a row. */
+int32_t wetts_wavlm_resample(const float* x, int64_t x_bs, int32_t B, int64_t L, int32_t orig, int32_t new_, int32_t width,
+                             const float* kernel, int32_t kernel_stride, float* padded, int64_t padded_stride, float* out,
+                             void* stream);
+/* The stages, each with the kernels the forward pass uses.
+ * _conv0: conv 0, its normalisation over time per (row, channel) (biased variance, eps 1e-5, affine), GELU
+ *   -> out [B][T0][conv_dim[0]].
+ * _conv: conv `layer` (1 ..) and GELU on x [B][Tin][conv_dim[layer - 1]] -> out [B][Tout][conv_dim[layer]].
+ * _project: LayerNorm -> normed [N][C], Linear -> out [N][hidden_size].
+ * _pos_conv: gelu of the grouped positional conv without its last column, x [B][T][hidden_size] -> out likewise.
+ * _attention: the gate of layer `layer` from x [B * T][hidden_size] -> gate [B * T][heads], then attention on
+ *   qkv [B * T][3 hidden_size] with logits q . k / sqrt(dk) + gate * bias(layer 0's table) -> out [B * T][hidden_size].
+ * _layer: encoder layer `layer` on x -> out (not x); workspace of wetts_wavlm_layer_workspace_bytes. */
+int32_t wetts_wavlm_conv0(const wetts_wavlm_t* w, const float* x, int64_t x_bs, int32_t B, int64_t L, float* out,
+                          void* stream);
+int32_t wetts_wavlm_conv(const wetts_wavlm_t* w, int32_t layer, const float* x, int32_t B, int64_t Tin, float* out,
+                         void* stream);
+int32_t wetts_wavlm_project(const wetts_wavlm_t* w, const float* x, int32_t N, float* normed, float* out, void* stream);
+int32_t wetts_wavlm_pos_conv(const wetts_wavlm_t* w, const float* x, int32_t B, int32_t T, float* out, void* stream);
+int32_t wetts_wavlm_attention(const wetts_wavlm_t* w, int32_t layer, const float* x, const float* qkv, int32_t B, int32_t T,
+                              float* gate, float* out, void* stream);
+int64_t wetts_wavlm_layer_workspace_bytes(const wetts_wavlm_t* w, int32_t B, int32_t T);
+int32_t wetts_wavlm_layer(const wetts_wavlm_t* w, int32_t layer, const float* x, int32_t B, int32_t T, float* out,
+                          void* workspace, void* stream);
+
+/* WavLMDiscriminator(slm_hidden, slm_layers, initial_channel) with use_spectral_norm = false.  Blob: pre.weight
+ * [c0][layers * hidden] (input channel layer * hidden + c), convs.N.weight and conv_post.weight tap-major
+ * [Cout][k][Cin], the biases; weight norm folded.  hidden: `layers` buffers [rows][T][hidden], buffer l at
+ * hidden + l * layer_stride -- wetts_wavlm_forward's output as it lies.  out [rows][T]. */
+int32_t wetts_wavlm_disc_blob_num_tensors(int32_t hidden, int32_t layers, int32_t c0);
+int32_t wetts_wavlm_disc_blob_tensor_info(int32_t hidden, int32_t layers, int32_t c0, int32_t index, char* name_buf,
+                                          size_t name_buf_len, int64_t* offset, int64_t* numel, int64_t shape[4]);
+int64_t wetts_wavlm_disc_blob_numel(int32_t hidden, int32_t layers, int32_t c0);
+int32_t wetts_wavlm_disc_create(int32_t hidden, int32_t layers, int32_t c0, const float* blob_dev, int64_t blob_numel,
+                                void* stream, wetts_wavlm_disc_t** out);
+void wetts_wavlm_disc_destroy(wetts_wavlm_disc_t* d);
+int64_t wetts_wavlm_disc_workspace_bytes(const wetts_wavlm_disc_t* d, int32_t rows, int32_t T);
+int32_t wetts_wavlm_disc_forward(const wetts_wavlm_disc_t* d, const float* hidden, int64_t layer_stride, int32_t rows,
+                                 int32_t T, float* out, void* workspace, void* stream);
+/* The stages: `pre` alone -> out [rows][T][c0] (one launch per layer, each reading its buffer in place and adding to
+ * out); the three k = 5 convs with leaky_relu(0.1) and conv_post on pre [rows][T][c0] -> out [rows][T]. */
+int32_t wetts_wavlm_disc_pre(const wetts_wavlm_disc_t* d, const float* hidden, int64_t layer_stride, int32_t rows, int32_t T,
+                             float* out, void* stream);
+int32_t wetts_wavlm_disc_convs(const wetts_wavlm_disc_t* d, const float* pre, int32_t rows, int32_t T, float* out,
+                               void* workspace, void* stream);
+
 /* ---- The 16-bit conv launches, one at a time (csrc/conv16_entry.hip) -----------------------------------------------
  *
  * Each entry runs ONE launch of the 16-bit decoder / flow (conv_bf16.hip, resblock16.hip, resblock2_stage16.hip,

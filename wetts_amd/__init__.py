@@ -7,15 +7,19 @@ from .config import HParams, get_hparams_from_file, make_config, MODEL_CONFIGS  
 from .models import SynthesizerTrn, load_checkpoint  # noqa: F401
 from .discriminators import (DurationDiscriminatorV1, DurationDiscriminatorV2,  # noqa: F401
                              MultiPeriodDiscriminator, MultiPeriodMultiResolutionDiscriminator,
-                             duration_discriminator_from_hparams)
+                             WavLMDiscriminator, duration_discriminator_from_hparams,
+                             wavlm_discriminator_from_hparams)
 from .frontend import (Frontend, FrontendModel, FrontendScores, FrontendSession, HostScores, Model,  # noqa: F401
                        compute_accuracy, prosody_f1)
 from .frontend_data import IGNORE_ID, FrontendDataset, VocabTokenizer, collate_fn, read_table  # noqa: F401
+from .losses import WavLMLoss  # noqa: F401
 from .mel_processing import (mel_spectrogram_torch, posterior_spectrogram, spec_to_mel_torch,  # noqa: F401
                              spectrogram_torch)
+from .wavlm import Resample, WavLM, load_wavlm  # noqa: F401
 
 __all__ = ["SynthesizerTrn", "MultiPeriodDiscriminator", "MultiPeriodMultiResolutionDiscriminator",
            "DurationDiscriminatorV1", "DurationDiscriminatorV2", "duration_discriminator_from_hparams",
+           "WavLMDiscriminator", "wavlm_discriminator_from_hparams", "WavLMLoss", "WavLM", "Resample", "load_wavlm",
            "FrontendModel", "FrontendSession", "Frontend", "Model", "FrontendScores", "HostScores", "compute_accuracy",
            "prosody_f1", "IGNORE_ID", "FrontendDataset", "VocabTokenizer", "collate_fn", "read_table",
            "load_checkpoint", "HParams", "get_hparams_from_file", "make_config",

@@ -84,6 +84,20 @@ class FrontendConfig(C.Structure):
 
 _FCFG = C.POINTER(FrontendConfig)
 
+WAVLM_MAX_CONV = 8
+
+
+class WavLMConfig(C.Structure):
+    """Mirror of wetts_wavlm_config_t."""
+    _fields_ = [("num_conv_layers", C.c_int32), ("conv_dim", C.c_int32 * WAVLM_MAX_CONV),
+                ("conv_kernel", C.c_int32 * WAVLM_MAX_CONV), ("conv_stride", C.c_int32 * WAVLM_MAX_CONV)] + \
+               [(n, C.c_int32) for n in ("hidden_size", "num_layers", "num_heads", "intermediate_size", "pos_kernel",
+                                          "pos_groups", "num_buckets", "max_bucket_distance")] + \
+               [("layer_norm_eps", C.c_float)]
+
+
+_WCFG = C.POINTER(WavLMConfig)
+
 # name -> (restype, argtypes); must list every symbol include/wetts_hip.h declares
 SIGNATURES = {
     "wetts_abi_version": (_I32, []),
@@ -223,6 +237,34 @@ SIGNATURES = {
     "wetts_frontend_score_workspace_bytes": (_I64, [_P, _I32, _I32]),
     "wetts_frontend_score": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "wetts_frontend_score_heads": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "wetts_wavlm_bucket": (_I32, [_I32, _I32, _I32]),
+    "wetts_wavlm_num_frames": (_I64, [_WCFG, _I64]),
+    "wetts_wavlm_blob_num_tensors": (_I32, [_WCFG]),
+    "wetts_wavlm_blob_tensor_info": (_I32, [_WCFG, _I32, C.c_char_p, C.c_size_t, C.POINTER(_I64), C.POINTER(_I64),
+                                            C.POINTER(_I64 * 4)]),
+    "wetts_wavlm_blob_numel": (_I64, [_WCFG]),
+    "wetts_wavlm_create": (_I32, [_WCFG, _P, _I64, _P, C.POINTER(_P)]),
+    "wetts_wavlm_destroy": (None, [_P]),
+    "wetts_wavlm_workspace_bytes": (_I64, [_P, _I32, _I64]),
+    "wetts_wavlm_forward": (_I32, [_P, _P, _I64, _I32, _I64, _P, _P, _I64, _P]),
+    "wetts_wavlm_resample": (_I32, [_P, _I64, _I32, _I64, _I32, _I32, _I32, _P, _I32, _P, _I64, _P, _P]),
+    "wetts_wavlm_conv0": (_I32, [_P, _P, _I64, _I32, _I64, _P, _P]),
+    "wetts_wavlm_conv": (_I32, [_P, _I32, _P, _I32, _I64, _P, _P]),
+    "wetts_wavlm_project": (_I32, [_P, _P, _I32, _P, _P, _P]),
+    "wetts_wavlm_pos_conv": (_I32, [_P, _P, _I32, _I32, _P, _P]),
+    "wetts_wavlm_attention": (_I32, [_P, _I32, _P, _P, _I32, _I32, _P, _P, _P]),
+    "wetts_wavlm_layer_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_wavlm_layer": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P, _P]),
+    "wetts_wavlm_disc_blob_num_tensors": (_I32, [_I32, _I32, _I32]),
+    "wetts_wavlm_disc_blob_tensor_info": (_I32, [_I32, _I32, _I32, _I32, C.c_char_p, C.c_size_t, C.POINTER(_I64),
+                                                 C.POINTER(_I64), C.POINTER(_I64 * 4)]),
+    "wetts_wavlm_disc_blob_numel": (_I64, [_I32, _I32, _I32]),
+    "wetts_wavlm_disc_create": (_I32, [_I32, _I32, _I32, _P, _I64, _P, C.POINTER(_P)]),
+    "wetts_wavlm_disc_destroy": (None, [_P]),
+    "wetts_wavlm_disc_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_wavlm_disc_forward": (_I32, [_P, _P, _I64, _I32, _I32, _P, _P, _P]),
+    "wetts_wavlm_disc_pre": (_I32, [_P, _P, _I64, _I32, _I32, _P, _P]),
+    "wetts_wavlm_disc_convs": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
     "wetts_conv16": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F,
                             _P]),
     "wetts_conv16_wn_gate": (_I32, [_P, _P, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),

@@ -486,3 +486,155 @@ def duration_discriminator_from_hparams(hps):
     cls = DurationDiscriminatorV1 if kind == "dur_disc_1" else DurationDiscriminatorV2
     gin = model["gin_channels"] if hps.data["n_speakers"] != 0 else 0
     return cls(model["hidden_channels"], model["hidden_channels"], 3, 0.1, gin_channels=gin)
+
+
+# ---- WavLMDiscriminator ------------------------------------------------------------------------------------------------
+class WavLMDiscriminator:
+    """model/discriminators.py:452-498: a 1x1 `pre` conv over the slm_layers * slm_hidden stacked WavLM hidden states,
+    three k = 5 convs with leaky_relu(0.1), and conv_post to one channel, all weight-normed -- as an evaluation module on
+    the device (csrc/wavlm.hip).  forward(x [B, slm_layers * slm_hidden, T]) -> [B, T] as the reference's; the WavLM loss
+    calls `on_hidden`, which reads the hidden-state buffers where they lie, so the stacked tensor is never formed."""
+
+    def __init__(self, slm_hidden=768, slm_layers=13, initial_channel=64, use_spectral_norm=False):
+        if use_spectral_norm:
+            raise NotImplementedError("use_spectral_norm=True is not supported: folding spectral norm needs the "
+                                      "power-iteration state (weight_u / weight_v); no checked-in recipe sets it")
+        self.slm_hidden, self.slm_layers, self.initial_channel = int(slm_hidden), int(slm_layers), int(initial_channel)
+        self.use_spectral_norm = False
+        self.training = False
+        self.layout()  # raises ValueError for a shape the kernels do not cover
+        self._blob = None
+        self._folded = None    # the folded tensors in the reference's shapes (state_dict)
+        self._handle = None
+        self._device = None
+
+    def layout(self):
+        """[(name, offset, numel, shape)] of the device blob: weight norm folded, convs tap-major [Cout][k][Cin]."""
+        from . import wavlm
+        lib = _lib.load()
+        a = (self.slm_hidden, self.slm_layers, self.initial_channel)
+        n = lib.wetts_wavlm_disc_blob_num_tensors(*a)
+        if n < 0:
+            raise ValueError(_lib.last_error())
+        return wavlm._read_layout(lambda i, *r: lib.wetts_wavlm_disc_blob_tensor_info(*a, i, *r), n)
+
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("this discriminator is evaluation only (no gradients)")
+        return self
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Reference-keyed (`pre`, `convs.N`, `conv_post`: bias and weight_g / weight_v, either weight-norm spelling, or
+        already folded weights).  Every tensor must be present."""
+        sd = checkpoint.fold_weight_norm(state_dict)
+        lay = self.layout()
+        blob = torch.zeros(lay[-1][1] + (lay[-1][2] + 3) // 4 * 4, dtype=torch.float32)
+        folded = {}
+        for name, off, numel, shape in lay:
+            if name not in sd:
+                raise KeyError(f"{name} is missing from the state_dict")
+            t = sd[name].detach().to(torch.float32)
+            # the reference's shape: [Cout, Cin, k] for a weight laid out tap-major [Cout][k][Cin] (pre: [c0][Cin], k = 1)
+            want = (shape[0], shape[-1], shape[1] if len(shape) == 3 else 1) if name.endswith(".weight") else tuple(shape)
+            if tuple(t.shape) != want:
+                raise ValueError(f"{name}: shape {tuple(t.shape)} in the state_dict, the discriminator has {want}")
+            folded[name] = t.clone()
+            if name.endswith(".weight"):
+                t = t.permute(0, 2, 1)
+            blob[off:off + numel] = t.reshape(-1)
+        self._blob, self._folded = blob, folded
+        if self._device is not None:
+            self._create()
+        return self
+
+    def state_dict(self):
+        """The folded tensors (weight norm collapsed), reference-keyed and in the reference's [Cout, Cin, k] shapes."""
+        self._require_blob()
+        return {k: v.clone() for k, v in self._folded.items()}
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("WavLMDiscriminator runs on a HIP device only (there is no CPU path)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self._device = device
+        if self._blob is not None:
+            self._create()
+        return self
+
+    def cuda(self, device=None):
+        return self.to("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+
+    def _require_blob(self):
+        if self._blob is None:
+            raise RuntimeError("no weights: call load_state_dict() first")
+
+    def _create(self):
+        self._destroy()
+        lib = _lib.load()
+        with torch.cuda.device(self._device):
+            dev = self._blob.to(self._device)
+            h = C.c_void_p()
+            _lib.check(lib.wetts_wavlm_disc_create(self.slm_hidden, self.slm_layers, self.initial_channel, _lib.ptr(dev),
+                                                   dev.numel(), _lib.current_stream_ptr(), C.byref(h)), "wavlm_disc_create")
+        self._handle = h
+
+    def _destroy(self):
+        if getattr(self, "_handle", None) is not None:
+            _lib.load().wetts_wavlm_disc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    def _require(self):
+        self._require_blob()
+        if self._handle is None:
+            raise RuntimeError("the discriminator is not on a device: call .to('cuda') / .cuda() first")
+
+    def on_hidden(self, hidden):
+        """hidden [slm_layers, R, T, slm_hidden] (contiguous float32, what WavLM computes) -> [R, T]."""
+        self._require()
+        if (not torch.is_tensor(hidden) or hidden.dim() != 4 or hidden.shape[0] != self.slm_layers or
+                hidden.shape[3] != self.slm_hidden or hidden.shape[1] < 1 or hidden.shape[2] < 1):
+            raise ValueError(f"hidden must be [{self.slm_layers}, rows, T, {self.slm_hidden}], got "
+                             f"{getattr(hidden, 'shape', type(hidden))}")
+        if hidden.device != self._device:
+            raise ValueError(f"hidden is on {hidden.device}, the discriminator on {self._device}")
+        hidden = hidden.to(torch.float32).contiguous()
+        _, R, T, H = hidden.shape
+        lib = _lib.load()
+        nbytes = int(lib.wetts_wavlm_disc_workspace_bytes(self._handle, R, T))
+        if nbytes < 0:
+            raise _lib.WettsError(f"wavlm_disc_workspace_bytes: {_lib.last_error()}")
+        with torch.cuda.device(self._device):
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self._device)
+            out = torch.empty(R, T, dtype=torch.float32, device=self._device)
+            _lib.check(lib.wetts_wavlm_disc_forward(self._handle, _lib.ptr(hidden), R * T * H, R, T, _lib.ptr(out),
+                                                    _lib.ptr(ws), _lib.current_stream_ptr()), "wavlm_disc_forward")
+        return out
+
+    def forward(self, x):
+        """discriminators.py:487-498: x [B, slm_layers * slm_hidden, T], channel layer * slm_hidden + c -> [B, T]."""
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != self.slm_layers * self.slm_hidden:
+            raise ValueError(f"x must be [B, {self.slm_layers * self.slm_hidden}, T], got {getattr(x, 'shape', type(x))}")
+        B, _, T = x.shape
+        return self.on_hidden(x.reshape(B, self.slm_layers, self.slm_hidden, T).permute(1, 0, 3, 2).contiguous())
+
+    __call__ = forward
+
+
+def wavlm_discriminator_from_hparams(hps):
+    """train.py:165-176: None unless hps.model.use_wd; else WavLMDiscriminator(slm_hidden, slm_nlayers,
+    slm_initial_channel)."""
+    model = hps.model
+    if not ("use_wd" in model.keys() and model["use_wd"]):
+        return None
+    return WavLMDiscriminator(model["slm_hidden"], model["slm_nlayers"], model["slm_initial_channel"])

@@ -201,7 +201,7 @@ def _flag(section, key):
 
 
 def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None, with_duration=False, e_q=None,
-                          eps_w=None, net_d=None, y=None, net_dur_disc=None, **reconstruct_kwargs):
+                          eps_w=None, net_d=None, y=None, net_dur_disc=None, wl=None, **reconstruct_kwargs):
     """train.py:400-432,486-488 for one batch, without gradients: net_g.reconstruct(...) in the place of net_g(...), the
     target mel (`spec` itself for a mel posterior encoder, else spec_to_mel_torch(spec)) sliced at ids_slice, the mel
     spectrogram of the decoded slice, and
@@ -231,12 +231,19 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
     values for the class in use: B terms and their sum for V1, whose two returned tensors the reference's zip walks row
     by row (each term a mean over ALL Tx positions, as train.py:446 notes), one term for V2 -- and dur_disc_per_utt,
     dur_gen_per_utt [B]: each utterance's mean over its own phonemes, which does not depend on the batch (NaN for an
-    utterance without any).  Without `net_dur_disc` nothing changes."""
+    utterance without any).  Without `net_dur_disc` nothing changes.
+
+    `wl` (a WavLMLoss; needs `y`, which may then come without `net_d`) adds train.py:467-471,496-498 on y_slice and
+    y_hat: loss_slm = wl.discriminator(y_slice, y_hat), loss_lm = wl(y_slice, y_hat), loss_lm_gen = wl.generator(y_hat)
+    (scalars) and loss_slm_per_utt, loss_lm_per_utt, loss_lm_gen_per_utt [B], from ONE WavLM pass over the 2B rows.
+    Without `wl` nothing changes."""
     d = hps.data
     if net_dur_disc is not None and not with_duration:
         raise ValueError("net_dur_disc needs with_duration=True: its inputs are that stage's x_enc, x_mask, logw_ and logw")
-    if (net_d is None) != (y is None):
+    if wl is None and (net_d is None) != (y is None):
         raise ValueError("net_d and y (the batch's waveform [B, 1, T_wav]) go together")
+    if wl is not None and y is None:
+        raise ValueError("wl needs y (the batch's waveform [B, 1, T_wav]): its terms compare y's slice with y_hat")
     if int(net_g.hop_length) != int(d.hop_length):
         raise ValueError(f"the model produces {net_g.hop_length} samples per frame but hps.data.hop_length is "
                          f"{d.hop_length}: the mel spectrogram of the decoded slice would not line up with the target")
@@ -274,4 +281,114 @@ def teacher_forced_losses(net_g, hps, x, x_lengths, spec, spec_lengths, sid=None
         out.update(loss_disc=loss_disc, loss_gen=loss_gen, loss_fm=loss_fm, loss_disc_per_utt=disc_pu,
                    loss_gen_per_utt=gen_pu, loss_fm_per_utt=fm_pu, losses_disc_r=r_losses, losses_disc_g=g_losses,
                    losses_gen=gen_losses, y_slice=y_slice)
+    if wl is not None:
+        out.update(wl.all_terms(commons.slice_segments(y, ids_slice, seg, scale=int(net_g.hop_length)), o))
     return out
+
+
+class WavLMLoss:
+    """losses.py:63-153 as an evaluation module on the device: `model` a transformers WavLM directory (config.json and
+    pytorch_model.bin; nothing is downloaded) or a wetts_amd.wavlm.WavLM, `wd` a WavLMDiscriminator (None: only
+    __call__ works), `model_sr` / `slm_sr` the rates of the resampler in front of WavLM -- a stand-in for
+    torchaudio.transforms.Resample, see wetts_amd/wavlm.py.  Waveforms are [B, L] or [B, 1, L] device tensors.
+
+        wl(wav, y_rec)                sum over the hidden states of mean |h(wav) - h(y_rec)|          (loss_lm)
+        wl.generator(y_rec)           mean (1 - wd(h(y_rec)))^2                                       (loss_lm_gen)
+        wl.discriminator(wav, y_rec)  mean (1 - wd(h(wav)))^2 + mean wd(h(y_rec))^2                   (loss_slm)
+        wl.discriminator_forward(wav) wd(h(wav)) [B, T]
+
+    Each returns a 0-d device tensor, or (loss, per_utt [B]) with `per_utterance=True`: the same from each utterance's
+    own elements.  wav and y_rec run through the resampler and WavLM as ONE batch of 2B rows; a row's values do not
+    depend on the batch, so the halves equal two calls bit for bit.  B = 1 works: the reference's `.squeeze()` drops the
+    batch dimension there and its WavLM call fails.  No gradients."""
+
+    def __init__(self, model, wd, model_sr, slm_sr=16000):
+        from . import wavlm
+        self.wavlm = model if isinstance(model, wavlm.WavLM) else wavlm.load_wavlm(model)
+        self.wd = wd
+        self.resample = wavlm.Resample(model_sr, slm_sr)
+        if wd is not None and (wd.slm_layers != self.wavlm.num_layers + 1 or wd.slm_hidden != self.wavlm.hidden_size):
+            raise ValueError(f"wd expects {wd.slm_layers} hidden states of {wd.slm_hidden} channels, WavLM gives "
+                             f"{self.wavlm.num_layers + 1} of {self.wavlm.hidden_size}")
+
+    def to(self, device):
+        self.wavlm.to(device)
+        if self.wd is not None:
+            self.wd.to(device)
+        return self
+
+    def cuda(self, device=None):
+        return self.to("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+
+    def eval(self):
+        return self
+
+    @staticmethod
+    def _rows(t, name):
+        if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[1] != 1):
+            raise ValueError(f"{name} must be a [B, L] or [B, 1, L] tensor, got {getattr(t, 'shape', type(t))}")
+        if t.device.type != "cuda":
+            raise ValueError(f"{name} must be on a HIP device (there is no CPU path)")
+        t = t.to(torch.float32)
+        return t.reshape(t.shape[0], t.shape[-1])
+
+    def hidden(self, *waves):
+        """The waveforms ([B, L] or [B, 1, L], one shape) as one batch -> [layers + 1, rows, T, hidden]."""
+        rows = [self._rows(w, "waveform") for w in waves]
+        for r in rows[1:]:
+            if tuple(r.shape) != tuple(rows[0].shape) or r.device != rows[0].device:
+                raise ValueError(f"the waveforms must have one shape and device, got {tuple(rows[0].shape)} and {tuple(r.shape)}")
+        x = rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+        if x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"empty waveform {tuple(x.shape)}")
+        n = self.resample.output_length(x.shape[1]) if self.resample.orig_freq != self.resample.new_freq else x.shape[1]
+        if self.wavlm.num_frames(n) < 1:  # before the resampler's launches
+            raise ValueError(f"{x.shape[1]} samples ({n} at the WavLM rate) are shorter than one WavLM frame")
+        if self.resample.orig_freq != self.resample.new_freq:
+            buf, n = self.resample._run(x)
+            x = buf[:, :n]
+        return self.wavlm._hidden(x)
+
+    def _need_wd(self):
+        if self.wd is None:
+            raise ValueError("this WavLMLoss has no discriminator (wd=None)")
+
+    def _lm(self, h, B):
+        total, _, _, pu = _disc_reduce(0, [l[:B] for l in h.unbind(0)], [l[B:] for l in h.unbind(0)], 1.0, "WavLM loss")
+        return total[0], pu
+
+    def forward(self, wav, y_rec, *, per_utterance=False):
+        h = self.hidden(wav, y_rec)
+        loss, pu = self._lm(h, h.shape[1] // 2)
+        return (loss, pu) if per_utterance else loss
+
+    __call__ = forward
+
+    def generator(self, y_rec, *, per_utterance=False):
+        self._need_wd()
+        total, _, pu = generator_loss([self.wd.on_hidden(self.hidden(y_rec))], per_utterance=True)
+        return (total, pu) if per_utterance else total
+
+    def discriminator(self, wav, y_rec, *, per_utterance=False):
+        self._need_wd()
+        d = self.wd.on_hidden(self.hidden(wav, y_rec))
+        B = d.shape[0] // 2
+        total, _, _, pu = discriminator_loss([d[:B]], [d[B:]], per_utterance=True)
+        return (total, pu) if per_utterance else total
+
+    def discriminator_forward(self, wav):
+        self._need_wd()
+        return self.wd.on_hidden(self.hidden(wav))
+
+    def all_terms(self, wav, y_rec):
+        """The three terms of a training step from one pass over the 2B rows -> dict loss_slm, loss_lm, loss_lm_gen and
+        their _per_utt [B]."""
+        self._need_wd()
+        h = self.hidden(wav, y_rec)
+        B = h.shape[1] // 2
+        lm, lm_pu = self._lm(h, B)
+        d = self.wd.on_hidden(h)
+        slm, _, _, slm_pu = discriminator_loss([d[:B]], [d[B:]], per_utterance=True)
+        gen, _, gen_pu = generator_loss([d[B:]], per_utterance=True)
+        return dict(loss_slm=slm, loss_lm=lm, loss_lm_gen=gen, loss_slm_per_utt=slm_pu, loss_lm_per_utt=lm_pu,
+                    loss_lm_gen_per_utt=gen_pu)

@@ -286,3 +286,75 @@ def blob_checksum(blob):
     b = blob.detach().to(torch.float64)
     idx = torch.arange(1, b.numel() + 1, dtype=torch.float64)
     return float((b * torch.cos(idx * 0.37)).sum())
+
+
+def make_wavlm_state_dict(config, seed=0):
+    """transformers-keyed state_dict of a WavLMModel in the base architecture for a WavLM config dict (config.json's
+    keys), deterministic in `seed` from a generator of its own; plain torch, no `transformers`.  Conv and Linear weights
+    randn * sqrt(gain / fan_in) (gain 2 in front of a GELU), biases 0.05 * randn, norm weights 1 + 0.1 * randn and biases
+    0.1 * randn, the positional conv as its weight-norm parametrisation (`original0` [1, 1, k], `original1`), the
+    relative position table randn and gru_rel_pos_const 1 + 0.3 * randn: the bias and its gate move the attention
+    logits by O(1), so a parity test sees them.  Carries masked_spec_embed, which the model constructs and never reads
+    in evaluation."""
+    g = torch.Generator().manual_seed(int(seed))
+    c = config
+    d, heads, ff = int(c["hidden_size"]), int(c["num_attention_heads"]), int(c["intermediate_size"])
+    dims, kernels = [int(v) for v in c["conv_dim"]], [int(v) for v in c["conv_kernel"]]
+    sd = {}
+
+    def randn(*shape):
+        return torch.randn(*shape, generator=g, dtype=torch.float32)
+
+    def lin(name, out, inp, gain=1.0):
+        sd[name + ".weight"] = randn(out, inp) * math.sqrt(gain / inp)
+        sd[name + ".bias"] = 0.05 * randn(out)
+
+    def norm(name, n):
+        sd[name + ".weight"] = 1.0 + 0.1 * randn(n)
+        sd[name + ".bias"] = 0.1 * randn(n)
+
+    sd["masked_spec_embed"] = randn(d)
+    for i, (co, k) in enumerate(zip(dims, kernels)):
+        ci = 1 if i == 0 else dims[i - 1]
+        sd[f"feature_extractor.conv_layers.{i}.conv.weight"] = randn(co, ci, k) * math.sqrt(2.0 / (ci * k))
+    norm("feature_extractor.conv_layers.0.layer_norm", dims[0])
+    norm("feature_projection.layer_norm", dims[-1])
+    lin("feature_projection.projection", d, dims[-1])
+    pk, cg = int(c["num_conv_pos_embeddings"]), d // int(c["num_conv_pos_embedding_groups"])
+    v = randn(d, cg, pk) * math.sqrt(2.0 / (cg * min(pk, 16)))
+    sd["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = (
+        torch.linalg.vector_norm(v, ord=2, dim=(0, 1), keepdim=True) * (1.0 + 0.05 * randn(1, 1, pk)))
+    sd["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = v
+    sd["encoder.pos_conv_embed.conv.bias"] = 0.05 * randn(d)
+    norm("encoder.layer_norm", d)
+    for i in range(int(c["num_hidden_layers"])):
+        p = f"encoder.layers.{i}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            lin(p + "attention." + n, d, d)
+        lin(p + "attention.gru_rel_pos_linear", 8, d // heads)
+        sd[p + "attention.gru_rel_pos_const"] = 1.0 + 0.3 * randn(1, heads, 1, 1)
+        if i == 0:
+            sd[p + "attention.rel_attn_embed.weight"] = randn(int(c["num_buckets"]), heads)
+        norm(p + "layer_norm", d)
+        lin(p + "feed_forward.intermediate_dense", ff, d, 2.0)
+        lin(p + "feed_forward.output_dense", d, ff)
+        norm(p + "final_layer_norm", d)
+    return sd
+
+
+def make_wavlm_discriminator_state_dict(slm_hidden=768, slm_layers=13, initial_channel=64, seed=0):
+    """Reference-keyed state_dict of WavLMDiscriminator (discriminators.py:452-485) with old-style weight-norm pairs on
+    every conv, deterministic in `seed` from a generator of its own; values as make_discriminator_state_dict gives them
+    (`pre`, which no activation follows, at gain 1)."""
+    g = torch.Generator().manual_seed(int(seed))
+    c0 = int(initial_channel)
+    sd = {}
+    for name, co, ci, k, gain in (("pre", c0, int(slm_hidden) * int(slm_layers), 1, 1.0), ("convs.0", 2 * c0, c0, 5, 2.0),
+                                  ("convs.1", 4 * c0, 2 * c0, 5, 2.0), ("convs.2", 4 * c0, 4 * c0, 5, 2.0),
+                                  ("conv_post", 1, 4 * c0, 3, 1.0)):
+        w = torch.randn(co, ci, k, generator=g, dtype=torch.float32) * math.sqrt(gain / (ci * k))
+        norm = torch.linalg.vector_norm(w, ord=2, dim=(1, 2), keepdim=True)
+        sd[name + ".weight_g"] = norm * (1.0 + 0.05 * torch.randn(co, 1, 1, generator=g))
+        sd[name + ".weight_v"] = w
+        sd[name + ".bias"] = 0.05 * torch.randn(co, generator=g, dtype=torch.float32)
+    return sd
