@@ -835,6 +835,40 @@ int32_t wetts_frontend_decide(const float* phone_prob, const float* prosody_prob
                               const int32_t* cand_len, int32_t N, int32_t P, int32_t R, int32_t max_cand, int32_t* choice,
                               int32_t* prosody, void* stream);
 
+/* ---- the 16-bit mode of the text frontend (csrc/frontend16.hip) ------------------------------------------------------
+ * precision: 0 = f32 (the default), 1 = bf16, 2 = f16, as wetts_set_decoder_precision counts them.  With 1 or 2 set on a
+ * handle, every Linear of the BERT layers and of `transform` (packed q|k|v, attention output, feed-forward in and out)
+ * reads BOTH operands rounded to the type (round to nearest even; an f16 operand out of range is +-inf), with exact
+ * products and f32 accumulation on the 16-bit MFMA; bias, GELU, ReLU and the residual stay f32 epilogues, and
+ * everything else -- embeddings, LayerNorms, attention, both classifiers, the softmaxes, the decisions, scoring -- is
+ * the f32 code unchanged.  _forward, _layer, _score and the workspace queries follow the handle's current mode.  The
+ * same call gives the same bits, and a valid token's bits depend neither on the padding nor on the order of the rows;
+ * but the kernel form is chosen by the token count, so a row alone and the same row in a batch need not agree to the
+ * last bit (they do at f32).
+ * _set_precision is a set-up call: it validates first, then packs the 16-bit copies of the weights on the device (it
+ * allocates and drains the device), and changes the handle only after every check has passed; 0 frees the copies.  The
+ * blob stays f32. */
+int32_t wetts_frontend_set_precision(wetts_frontend_t* f, int32_t precision);
+/* The Linear of that mode alone, for tests: f32 x [N][K], weight [M][K], bias [M], residual [N][M] (epilogue 3) and out
+ * [N][M], every one of them 16-byte aligned; the weight is packed into `workspace` (16-byte aligned, >=
+ * _linear16_workspace_bytes(K, M) bytes) on `stream` first.  precision 1 or 2.  form: 0 = the launcher's choice by N and
+ * M (what the forward pass uses: 1 up to 64 tokens, beyond them 3 where ceil(M / 128) * ceil(N / 128) >= 512 and 2
+ * otherwise), 1 = K split over the block's waves (64 tokens per block), 2 / 3 = tiled GEMM with 64 / 128 tokens per
+ * block.  K % 8 == 0, M % 4 == 0; everything is checked before the first launch. */
+int64_t wetts_frontend_linear16_workspace_bytes(int32_t K, int32_t M);
+int32_t wetts_frontend_linear16(const float* x, const float* weight, const float* bias, const float* residual, int32_t N,
+                                int32_t K, int32_t M, int32_t epilogue, int32_t precision, int32_t form, float* out,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+/* For the project's own tests and bench tools only; an application needs none of the three.
+ * _get_precision: the handle's mode, 0, 1 or 2; negative for a null handle.
+ * _linear16_form: the form (1, 2 or 3) that form 0 takes at N tokens and M channels; negative for a bad shape.
+ * form | WETTS_FRONTEND_LINEAR16_BENCH_PACKED in wetts_frontend_linear16: the workspace still holds the packed weight of
+ * the caller's previous call with the same weight and precision and is not packed again, so that a measurement times
+ * the Linear alone.  Nothing can check that claim: a stale workspace gives wrong results silently. */
+int32_t wetts_frontend_get_precision(const wetts_frontend_t* f);
+int32_t wetts_frontend_linear16_form(int32_t N, int32_t M);
+#define WETTS_FRONTEND_LINEAR16_BENCH_PACKED 16
+
 /* ---- scoring the text frontend (csrc/frontend_score.hip) ------------------------------------------------------------
  * The validation pass of frontend/train.py:43-94 (two F.cross_entropy(.., ignore_index=-100) terms, compute_accuracy),
  * the masked accuracy counts of frontend/test_polyphone.py:72-86 and the counts behind the three binary F1 scores of

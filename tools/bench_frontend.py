@@ -8,11 +8,20 @@ weight-streaming bound (the bytes of every weight matrix read once over the 6.3 
 microarchitecture notes list as achievable); for the batched shapes the share of the f32 MFMA peak (256 CUs x 4 SIMDs x
 64 FLOP / clock at 2.4 GHz = 157 TFLOP/s) the Linear layers reach; and the same model written with torch.nn.functional
 on the same device and weights (a restatement inside this tool: no `transformers`).  Prints one JSON line.
-    python tools/bench_frontend.py [--steps 20] [--warmup 5] [--out profiles/frontend_bench.json]"""
+    python tools/bench_frontend.py [--steps 20] [--warmup 5] [--out profiles/frontend_bench.json]
+
+With --dtype (f32, bf16, f16; several may be given) the tool compares the modes of FrontendModel.set_dtype instead: per
+shape, the named modes, the same model in torch.nn.functional at f32 and under bf16 autocast, all in ONE process,
+alternating, `--repeats` times each after a warm-up of every variant -- median and spread (min, max) of the per-call
+device-event times -- and each Linear of a layer alone: the f32 kernel and every kernel form of the 16-bit one (the
+weight packed once, outside the timed calls), with the achieved FLOP/s of the launcher's choice over the 2.5 PFLOP/s
+dense bf16 MFMA peak (a kernel figure).  470 + 5 classes as in the reference lexicon.
+    python tools/bench_frontend.py --dtype f32 bf16 f16 [--repeats 5] [--out profiles/frontend16_bench.json]"""
 import argparse
 import json
 import math
 import os
+import statistics
 import sys
 
 import torch
@@ -28,6 +37,9 @@ BERT = dict(_name_or_path="bert-chinese-base", vocab_size=21128, hidden_size=768
 POLYPHONES, PROSODY = 1000, 5
 SHAPES = ((1, 16), (1, 48), (16, 64), (16, 256))
 COPY_BW, MFMA_PEAK = 6.3e12, 256 * 4 * 64 * 2.4e9
+BF16_PEAK = 2.5e15  # dense bf16 / f16 MFMA, the microarchitecture notes' figure
+PRECISION = {"f32": 0, "bf16": 1, "f16": 2}
+BENCH_PACKED = 16  # WETTS_FRONTEND_LINEAR16_BENCH_PACKED: the workspace already holds this weight, packed by the call before
 
 
 def timed(fn, steps, warmup):
@@ -41,6 +53,21 @@ def timed(fn, steps, warmup):
     e[1].record()
     torch.cuda.synchronize()
     return e[0].elapsed_time(e[1]) / steps
+
+
+def spread(fns, steps, warmup, repeats):
+    """{name: (median, min, max) ms per call}; the functions alternate within every repeat, after a warm-up of each."""
+    for fn in fns.values():
+        timed(fn, 1, warmup)
+    runs = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            runs[k].append(timed(fn, steps, 0))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in runs.items()}
+
+
+def _mms(v):
+    return dict(median=round(v[0], 4), min=round(v[1], 4), max=round(v[2], 4))
 
 
 def torch_forward(W, cfg, ids, mask):
@@ -81,7 +108,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the result line to this file")
+    ap.add_argument("--dtype", nargs="+", choices=tuple(PRECISION), default=None,
+                    help="compare these modes of FrontendModel.set_dtype (see the module text); default: the f32 report")
+    ap.add_argument("--repeats", type=int, default=5, help="with --dtype: alternating repeats per variant")
     a = ap.parse_args()
+    if a.dtype:
+        return compare(a)
     cfg = frontend_config(POLYPHONES, PROSODY, BERT)
     sd = synth.make_frontend_state_dict(cfg, 5)
     net = FrontendModel(POLYPHONES, PROSODY, BERT).load_state_dict(sd).to("cuda")
@@ -135,6 +167,92 @@ def main():
         if B > 1:
             row["linear_share_of_f32_mfma_peak"] = round(2 * N * (4 * d * d + 2 * d * ff) / (lin_ms * 1e-3) / MFMA_PEAK, 3)
             row["forward_share_of_f32_mfma_peak"] = round(N * lin_flops_per_token / (ms * 1e-3) / MFMA_PEAK, 3)
+        line["shapes"][f"{B}x{T}"] = row
+    print(json.dumps(line))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(line) + "\n")
+
+
+def compare(a):
+    """The --dtype report."""
+    P_, R_ = 470, 5
+    cfg = frontend_config(P_, R_, BERT)
+    sd = synth.make_frontend_state_dict(cfg, 5)
+    modes = list(dict.fromkeys(a.dtype))
+    nets = {m: FrontendModel(P_, R_, BERT).set_dtype(m).load_state_dict(sd).to("cuda") for m in modes}
+    W = {k: v.cuda() for k, v in sd.items() if v.is_floating_point()}
+    d, ff, L = cfg["hidden_size"], cfg["intermediate_size"], cfg["num_layers"]
+    for i in range(L):
+        p = f"bert.encoder.layer.{i}."
+        for kind in ("weight", "bias"):
+            W[p + "qkv." + kind] = torch.cat([W.pop(p + f"attention.self.{n}.{kind}") for n in ("query", "key", "value")], 0)
+    lin_elems = L * (4 * d * d + 2 * d * ff) + 4 * d * d + 2 * d * cfg["transform_ff"]
+    line = dict(tool="bench_frontend --dtype", modes=modes, steps=a.steps, repeats=a.repeats, launches_per_call=7 * (L + 1) + 2,
+                config=dict(layers=L, hidden=d, heads=cfg["num_heads"], intermediate=ff, polyphones=P_, prosody=R_),
+                linear_weight_bytes=dict(f32=4 * lin_elems, bf16=2 * lin_elems, f16=2 * lin_elems),
+                bf16_mfma_peak_flops=BF16_PEAK, device=torch.cuda.get_device_name(), shapes={})
+    lib, P, s = _lib.load(), _lib.ptr, _lib.current_stream_ptr
+    p0 = "bert.encoder.layer.0."
+    gen = torch.Generator().manual_seed(0)
+    for B, T in SHAPES:
+        N = B * T
+        ids = torch.randint(0, cfg["vocab_size"], (B, T), generator=gen).cuda()
+        mask = torch.ones(B, T, dtype=torch.int64).cuda()
+        fns = {m: (lambda n=n: n._launch(ids, None, mask, True)) for m, n in nets.items()}
+        fns["torch_functional_f32"] = lambda: torch_forward(W, cfg, ids, mask)
+
+        def autocast():
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                return torch_forward(W, cfg, ids, mask)
+
+        fns["torch_functional_bf16_autocast"] = autocast
+        with torch.no_grad():
+            t = spread(fns, a.steps, a.warmup, a.repeats)
+        row = dict(forward_ms={k: _mms(v) for k, v in t.items()})
+        if "f32" in t:
+            for m in modes:
+                if m != "f32":
+                    row[f"f32_over_{m}"] = round(t["f32"][0] / t[m][0], 3)
+                    row[f"{m}_faster_beyond_the_spread"] = bool(t[m][2] < t["f32"][1])
+        # the stages of one layer alone: attention and LayerNorm (f32 in every mode), each Linear in f32 and in every form
+        h, mf = torch.randn(N, d, device="cuda"), torch.ones(N, device="cuda")
+        qkv, ctx, o, f1 = (torch.empty(N, c, device="cuda") for c in (3 * d, d, d, ff))
+        w = lambda n: P(W[p0 + n])  # noqa: E731
+        linears = dict(qkv_linear=(h, "qkv", None, d, 3 * d, 0, qkv), out_linear_residual=(ctx, "attention.output.dense", h, d, d, 3, o),
+                       ff1_linear_gelu=(h, "intermediate.dense", None, d, ff, 1, f1),
+                       ff2_linear_residual=(f1, "output.dense", h, ff, d, 3, o))
+        st = dict(attention=lambda: lib.wetts_frontend_attention(P(qkv), P(mf), B, T, cfg["num_heads"], d // cfg["num_heads"], P(ctx), s()),
+                  layer_norm=lambda: lib.wetts_frontend_add_layer_norm(P(o), None, w("output.LayerNorm.weight"),
+                                                                       w("output.LayerNorm.bias"), 1e-12, N, d, P(ctx), s()))
+        keep = []
+        for name, (x, wn, res, K, M, epi, out) in linears.items():
+            st[name + ".f32"] = (lambda x=x, wn=wn, res=res, K=K, M=M, epi=epi, out=out:
+                                 lib.wetts_frontend_linear(P(x), w(wn + ".weight"), w(wn + ".bias"), P(res), N, K, M, epi, P(out), s()))
+            for m in modes:
+                if m == "f32":
+                    continue
+                ws = torch.empty(K * M // 2, device="cuda")
+                keep.append(ws)
+                _lib.check(lib.wetts_frontend_linear16(P(x), w(wn + ".weight"), w(wn + ".bias"), P(res), N, K, M, epi, PRECISION[m],
+                                                       0, P(out), P(ws), 2 * K * M, s()), "linear16")  # packs the weight once
+                for form in (0, 1, 2, 3):
+                    st[f"{name}.{m}.form{form}"] = (
+                        lambda x=x, wn=wn, res=res, K=K, M=M, epi=epi, out=out, m=m, form=form, ws=ws:
+                        lib.wetts_frontend_linear16(P(x), w(wn + ".weight"), w(wn + ".bias"), P(res), N, K, M, epi, PRECISION[m],
+                                                    form | BENCH_PACKED, P(out), P(ws), 2 * K * M, s()))
+        ts = spread(st, a.steps, a.warmup, a.repeats)
+        row["stage_ms"] = {k: _mms(v) for k, v in ts.items()}
+        row["launcher_form"] = {k: int(lib.wetts_frontend_linear16_form(N, M)) for k, (_, _, _, _, M, _, _) in linears.items()}
+        for m in modes:
+            sfx = ".f32" if m == "f32" else f".{m}.form0"
+            lin = sum(ts[k + sfx][0] for k in linears)
+            layer = lin + ts["attention"][0] + 2 * ts["layer_norm"][0]
+            row[f"layer_ms_{m}"] = round(layer, 4)
+            row[f"attention_share_of_layer_{m}"] = round(ts["attention"][0] / layer, 3)
+            row[f"linear_share_of_layer_{m}"] = round(lin / layer, 3)
+            if m != "f32" and B > 1:
+                row[f"linear_kernels_share_of_bf16_mfma_peak_{m}"] = round(2 * N * (4 * d * d + 2 * d * ff) / (lin * 1e-3) / BF16_PEAK, 4)
         line["shapes"][f"{B}x{T}"] = row
     print(json.dumps(line))
     if a.out:

@@ -10,7 +10,8 @@ The two ways alternate inside one process, `--repeats` times each after a warm-u
 median and the spread (min, max) of the per-call device-event times over the repeats, and their ratio.  Before timing,
 the losses and predictions of the two ways are compared (the losses within 1e-5 relative, the predictions equal).
 Prints one JSON line.
-    python tools/bench_frontend_score.py [--steps 20] [--warmup 5] [--repeats 5] [--out profiles/frontend_score_bench.json]"""
+    python tools/bench_frontend_score.py [--steps 20] [--warmup 5] [--repeats 5] [--out profiles/frontend_score_bench.json]
+--dtype f32 | bf16 | f16 runs both ways in that mode of FrontendModel.set_dtype and names it in the line."""
 import argparse
 import json
 import os
@@ -47,15 +48,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the result line to this file")
+    ap.add_argument("--dtype", choices=("f32", "bf16", "f16"), default=None,
+                    help="the mode of FrontendModel.set_dtype both ways run in (default: f32; the line then names it)")
     a = ap.parse_args()
     cfg = frontend_config(POLYPHONES, PROSODY, BERT)
     net = FrontendModel(POLYPHONES, PROSODY, BERT).load_state_dict(synth.make_frontend_state_dict(cfg, 5)).to("cuda")
+    if a.dtype:
+        net.set_dtype(a.dtype)
     d = cfg["hidden_size"]
     line = dict(tool="bench_frontend_score", config=dict(layers=cfg["num_layers"], hidden=d, polyphones=POLYPHONES,
                                                          prosody=PROSODY,
                                                          class_tiles=-(-POLYPHONES // 32) + -(-PROSODY // 32)),
                 steps=a.steps, repeats=a.repeats, device=torch.cuda.get_device_name(),
                 baseline="forward() logits + F.cross_entropy(ignore_index=-100) + argmax on the device", shapes={})
+    if a.dtype:
+        line["dtype"] = a.dtype
     lib, P, s = _lib.load(), _lib.ptr, _lib.current_stream_ptr
     gen = torch.Generator().manual_seed(0)
     for B, T in SHAPES:

@@ -237,6 +237,11 @@ SIGNATURES = {
     "wetts_frontend_score_workspace_bytes": (_I64, [_P, _I32, _I32]),
     "wetts_frontend_score": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "wetts_frontend_score_heads": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "wetts_frontend_set_precision": (_I32, [_P, _I32]),
+    "wetts_frontend_get_precision": (_I32, [_P]),
+    "wetts_frontend_linear16_form": (_I32, [_I32, _I32]),
+    "wetts_frontend_linear16_workspace_bytes": (_I64, [_I32, _I32]),
+    "wetts_frontend_linear16": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
     "wetts_wavlm_bucket": (_I32, [_I32, _I32, _I32]),
     "wetts_wavlm_num_frames": (_I64, [_WCFG, _I64]),
     "wetts_wavlm_blob_num_tensors": (_I32, [_WCFG]),

@@ -1,6 +1,7 @@
 // The text frontend (frontend/model.py:21-73): an HF BertModel (absolute positions, last_hidden_state), one
 // nn.TransformerEncoderLayer (batch_first, post-norm, ReLU) and the polyphone / prosody classifiers, without gradients.
-// All f32, wave64, on the caller's stream; a blob and a handle of its own.
+// All f32, wave64, on the caller's stream; a blob and a handle of its own.  (wetts_frontend_set_precision, frontend16.hip:
+// the layers' Linears alone may read bf16 / f16 operands; every kernel of this file is the same in that mode.)
 //
 // Layout.  Activations are token-major, [N = B * T][C]: a token's channels are contiguous, so the embedding gather, the
 // LayerNorms, the classifier rows and the [B, T, classes] outputs are all row operations, and BOTH operands of a Linear
@@ -615,16 +616,23 @@ static void fe_regions(const wetts_frontend_config_t& c, int B, int T, int64_t o
   for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + align_up(sizes[i], 64);
 }
 
-// one post-norm layer on h (in place); h2, ctx, qkv, ff are scratch
+// one post-norm layer on h (in place); h2, ctx, qkv, ff are scratch.  prec != 0: the four Linears read 16-bit operands
+// (frontend16.hip); everything between them is the f32 code of prec == 0.
 static int32_t fe_run_block(const FeBlock& k, int d, float* h, float* h2, float* ctx, float* qkv, float* ff,
-                            const float* maskf, int B, int T, hipStream_t s) {
+                            const float* maskf, int B, int T, int prec, hipStream_t s) {
   const int N = B * T;
-  WETTS_TRY(fe_launch_linear(h, k.wqkv, k.bqkv, nullptr, qkv, N, d, 3 * d, FE_EPI_BIAS, s));
+  auto linear = [&](const float* x, const float* w, const unsigned short* w16, const float* bias, const float* res, float* y,
+                    int K, int M, int epi) -> int32_t {
+    if (prec == 0) return fe_launch_linear(x, w, bias, res, y, N, K, M, epi, s);
+    WETTS_REQUIRE(w16 != nullptr, "frontend: the 16-bit weights are not packed");
+    return fe_launch_linear16(x, w16, bias, res, y, N, K, M, epi, prec, 0, s);
+  };
+  WETTS_TRY(linear(h, k.wqkv, k.wqkv16, k.bqkv, nullptr, qkv, d, 3 * d, FE_EPI_BIAS));
   WETTS_TRY(fe_launch_attention(qkv, maskf, ctx, B, T, k.heads, d / k.heads, s));
-  WETTS_TRY(fe_launch_linear(ctx, k.wo, k.bo, h, h2, N, d, d, FE_EPI_RES, s));
+  WETTS_TRY(linear(ctx, k.wo, k.wo16, k.bo, h, h2, d, d, FE_EPI_RES));
   WETTS_TRY(fe_launch_add_ln(h2, nullptr, k.g1, k.b1, k.eps, N, d, h, s));
-  WETTS_TRY(fe_launch_linear(h, k.w1, k.bb1, nullptr, ff, N, d, k.ff, k.act, s));
-  WETTS_TRY(fe_launch_linear(ff, k.w2, k.bb2, h, h2, N, k.ff, d, FE_EPI_RES, s));
+  WETTS_TRY(linear(h, k.w1, k.w116, k.bb1, nullptr, ff, d, k.ff, k.act));
+  WETTS_TRY(linear(ff, k.w2, k.w216, k.bb2, h, h2, k.ff, d, FE_EPI_RES));
   return fe_launch_add_ln(h2, nullptr, k.g2, k.b2, k.eps, N, d, h, s);
 }
 
@@ -645,7 +653,7 @@ int32_t fe_hidden(const wetts_frontend* h, const int64_t* ids, const int64_t* tt
   float* ws = (float*)workspace;
   float *hb = ws + off[0], *h2 = ws + off[1], *ctx = ws + off[2], *qkv = ws + off[3], *ff = ws + off[4], *mf = ws + off[5];
   WETTS_TRY(fe_launch_embed(h, ids, tts, mask, B, T, hb, mf, status, s));
-  for (const FeBlock& k : h->blocks) WETTS_TRY(fe_run_block(k, h->cfg.hidden_size, hb, h2, ctx, qkv, ff, mf, B, T, s));
+  for (const FeBlock& k : h->blocks) WETTS_TRY(fe_run_block(k, h->cfg.hidden_size, hb, h2, ctx, qkv, ff, mf, B, T, h->precision, s));
   *x = hb;
   *maskf = mf;
   return WETTS_OK;
@@ -765,6 +773,7 @@ int32_t wetts_frontend_create(const wetts_frontend_config_t* cfg, const float* b
 void wetts_frontend_destroy(wetts_frontend_t* h) {
   if (!h) return;
   if (h->blob) (void)hipFree(h->blob);
+  if (h->w16) (void)hipFree(h->w16);
   delete h;
 }
 
@@ -826,7 +835,7 @@ int32_t wetts_frontend_layer(const wetts_frontend_t* h, int32_t layer, float* x,
   fe_regions(h->cfg, B, T, off);
   float* ws = (float*)workspace;
   return fe_run_block(h->blocks[layer], h->cfg.hidden_size, x, ws + off[1], ws + off[2], ws + off[3], ws + off[4], key_mask, B,
-                      T, (hipStream_t)stream);
+                      T, h->precision, (hipStream_t)stream);
 }
 
 int32_t wetts_frontend_decide(const float* phone_prob, const float* prosody_prob, const int32_t* cand, const int32_t* cand_len,

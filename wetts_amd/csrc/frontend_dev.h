@@ -29,6 +29,8 @@ struct FeBlock {  // one post-norm transformer layer
   const float *wqkv, *bqkv, *wo, *bo, *g1, *b1, *w1, *bb1, *w2, *bb2, *g2, *b2;
   int heads, ff, act;
   float eps;
+  // the 16-bit copies of wqkv, wo, w1, w2 (natural [M][K] layout), null in f32 mode: wetts_frontend_set_precision
+  const unsigned short *wqkv16 = nullptr, *wo16 = nullptr, *w116 = nullptr, *w216 = nullptr;
 };
 
 }  // namespace wetts
@@ -39,6 +41,8 @@ struct wetts_frontend {
   const float *word = nullptr, *pos = nullptr, *type = nullptr, *eg = nullptr, *eb = nullptr;
   std::vector<wetts::FeBlock> blocks;  // the BERT layers, then `transform`
   const float *wp = nullptr, *bp = nullptr, *wr = nullptr, *br = nullptr;
+  int precision = 0;              // 0 = f32, 1 = bf16, 2 = f16: the operands of the layers' Linears (csrc/frontend16.hip)
+  unsigned short* w16 = nullptr;  // one allocation behind the blocks' 16-bit pointers
 };
 
 namespace wetts {
@@ -49,5 +53,10 @@ int64_t fe_workspace_floats(const wetts_frontend* h, int B, int T);
 // (1.0 / 0.0) point into `workspace`.  Checks B, T like wetts_frontend_forward; `what` names the caller in messages.
 int32_t fe_hidden(const wetts_frontend* h, const int64_t* ids, const int64_t* tts, const int64_t* mask, int B, int T,
                   void* workspace, int32_t* status, hipStream_t s, const char* what, const float** x, const float** maskf);
+
+// csrc/frontend16.hip: fe_launch_linear's contract on 16-bit operands; x, bias, res and y stay f32, w16 is the packed
+// copy of the weight.  precision 1 = bf16, 2 = f16; form 0 = by N and M, 1 = K-split, 2 / 3 = tiled with 64 / 128 tokens.
+int32_t fe_launch_linear16(const float* x, const unsigned short* w16, const float* bias, const float* res, float* y, int N,
+                           int K, int M, int epi, int precision, int form, hipStream_t s);
 
 }  // namespace wetts

@@ -22,6 +22,18 @@ from .frontend_data import IGNORE_ID  # noqa: F401  (-100, frontend/dataset.py:1
 
 # frontend/model.py:33-42: substring of bert_name_or_path -> (d_model, nhead, dim_feedforward) of `transform`
 TRANSFORM_SHAPES = (("bert-chinese-base", (768, 8, 2048)), ("TinyBERT_4L_zh_backup", (312, 12, 1200)))
+# what set_dtype accepts (SynthesizerTrn.set_decoder_dtype's names) -> wetts_frontend_set_precision's number
+PRECISIONS = {torch.float32: 0, "f32": 0, "fp32": 0, torch.bfloat16: 1, "bf16": 1, torch.float16: 2, "f16": 2, "fp16": 2}
+
+
+def frontend_precision(dtype):
+    """0 (f32) / 1 (bf16) / 2 (f16) of a dtype or name; None means f32.  ValueError for anything else."""
+    if dtype is None:
+        return 0
+    try:
+        return PRECISIONS[dtype]
+    except (KeyError, TypeError):
+        raise ValueError(f"dtype must be torch.float32 / bfloat16 / float16 or 'f32' / 'bf16' / 'f16', got {dtype!r}") from None
 
 
 def transform_shape(bert_name_or_path):
@@ -79,6 +91,7 @@ class FrontendModel:
         self._handle = None
         self._device = None
         self._status = None
+        self._precision = 0
 
     # ---- nn.Module-like surface ----
     def eval(self):
@@ -117,6 +130,23 @@ class FrontendModel:
     def cuda(self, device=None):
         return self.to("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
 
+    def set_dtype(self, dtype):
+        """The operands of the Linears of the BERT layers and of `transform`: torch.float32 (the default), torch.bfloat16
+        or torch.float16 (or "f32" / "bf16" / "f16"): both operands rounded to the type, exact products, f32
+        accumulation and f32 epilogues; embeddings, LayerNorms, attention, classifiers, softmaxes, decisions and scoring
+        stay f32.  May be called before or after .to(device); on a device it packs the 16-bit weight copies (a set-up
+        call: it allocates and drains), float32 frees them.  bfloat16 is the recommended type."""
+        prec = frontend_precision(dtype)
+        if self._handle is not None:
+            with torch.cuda.device(self._device):
+                _lib.check(_lib.load().wetts_frontend_set_precision(self._handle, prec), "frontend_set_precision")
+        self._precision = prec
+        return self
+
+    @property
+    def dtype(self):
+        return (torch.float32, torch.bfloat16, torch.float16)[self._precision]
+
     @property
     def device(self):
         return self._device
@@ -135,7 +165,9 @@ class FrontendModel:
             _lib.check(lib.wetts_frontend_create(C.byref(cfg), _lib.ptr(dev), dev.numel(), _lib.current_stream_ptr(),
                                                  C.byref(h)), "frontend_create")
             self._status = torch.zeros(1, dtype=torch.int32, device=self._device)
-        self._handle = h
+            self._handle = h
+            if self._precision:
+                _lib.check(lib.wetts_frontend_set_precision(h, self._precision), "frontend_set_precision")
 
     def _destroy(self):
         if self._handle is not None:
@@ -374,16 +406,17 @@ class HostScores:
         return prosody_f1(self.counts, exclude_end)
 
 
-def load_frontend_model(model_dir, device="cuda"):
+def load_frontend_model(model_dir, device="cuda", dtype=None):
     """FrontendModel from `final.pt` (frontend/train.py:215's state_dict) and `config.json` (the BERT's HF config) in
-    model_dir.  The classifier widths are read from the checkpoint."""
+    model_dir.  The classifier widths are read from the checkpoint.  `dtype`: FrontendModel.set_dtype's argument
+    (None: float32)."""
     sd = torch.load(os.path.join(model_dir, "final.pt"), map_location="cpu", weights_only=True)
     for k in ("phone_classifier.weight", "prosody_classifier.weight"):
         if k not in sd:
             raise KeyError(f"{k} missing from {os.path.join(model_dir, 'final.pt')}")
     model = FrontendModel(sd["phone_classifier.weight"].shape[0], sd["prosody_classifier.weight"].shape[0],
                           os.path.join(model_dir, "config.json"))
-    return model.load_state_dict(sd).to(device)
+    return model.set_dtype(dtype if dtype is not None else torch.float32).load_state_dict(sd).to(device)
 
 
 class _Arg:
@@ -395,8 +428,12 @@ class FrontendSession:
     """onnxruntime-shaped session of the frontend's exported graph (export_onnx.py:72-91): input `input` [1, T] int64,
     outputs `polyphone_output` [1, T, P] and `prosody_output` [1, T, R], the two softmaxes of export_forward."""
 
-    def __init__(self, model_or_dir, device="cuda"):
-        self.model = model_or_dir if isinstance(model_or_dir, FrontendModel) else load_frontend_model(model_or_dir, device)
+    def __init__(self, model_or_dir, device="cuda", dtype=None):
+        """`dtype`: FrontendModel.set_dtype's argument; None leaves a given model as it is (float32 for a directory)."""
+        if isinstance(model_or_dir, FrontendModel):
+            self.model = model_or_dir if dtype is None else model_or_dir.set_dtype(dtype)
+        else:
+            self.model = load_frontend_model(model_or_dir, device, dtype)
         self.model._require()
 
     def get_inputs(self):
@@ -432,9 +469,11 @@ class Frontend:
     """cli/frontend.py's Frontend: the same table readers, the same compute(text).  model_dir holds `final.pt` and
     `config.json` (nothing here reads `final.onnx`), `vocab.txt` and `lexicon/{polyphone.txt, pinyin_dict.txt,
     lexicon.txt}`.  `session=`: any object with the exported graph's run() (then the decisions are the reference's host
-    code on its outputs); by default the model runs on the device and the decisions are made there too."""
+    code on its outputs); by default the model runs on the device and the decisions are made there too.  `dtype`:
+    FrontendModel.set_dtype's argument for that model (None: float32); a given session keeps its own."""
 
-    def __init__(self, model_dir, session=None, device="cuda"):
+    def __init__(self, model_dir, session=None, device="cuda", dtype=None):
+        frontend_precision(dtype)  # (a bad dtype is refused before anything is read)
         self.token2id = self.read_list(os.path.join(model_dir, "vocab.txt"))
         self.polyphone2id = self.read_list(os.path.join(model_dir, "lexicon", "polyphone.txt"))
         self.id2polyphone = {v: k for k, v in self.polyphone2id.items()}
@@ -442,7 +481,7 @@ class Frontend:
         self.pinyin2phones = self.read_pinyin2phones(os.path.join(model_dir, "lexicon", "lexicon.txt"))
         self.model = None
         if session is None:
-            self.model = load_frontend_model(model_dir, device)
+            self.model = load_frontend_model(model_dir, device, dtype)
             if self.model.num_polyphones != len(self.polyphone2id):
                 raise ValueError(f"final.pt classifies {self.model.num_polyphones} polyphones, polyphone.txt lists "
                                  f"{len(self.polyphone2id)}")

@@ -1,7 +1,7 @@
 """Scoring a frontend checkpoint on the device, with the reference scripts' flags and printed lines:
 
     python -m wetts_amd.frontend_eval polyphone --polyphone_dict D --prosody_dict D --test_data F --checkpoint C \\
-        --bert_name_or_path DIR [--batch_size 32]                       # frontend/test_polyphone.py: "Accuracy: .."
+        --bert_name_or_path DIR [--batch_size 32] [--dtype f32|bf16|f16] # frontend/test_polyphone.py: "Accuracy: .."
     python -m wetts_amd.frontend_eval prosody   ... [--exclude_end]     # frontend/test_prosody.py: "pw f1_score .."
     python -m wetts_amd.frontend_eval cv --cv_polyphone_data F --cv_prosody_data F [--polyphone_weight 0.5] ...
                                                                         # the CV pass of frontend/train.py:43-94
@@ -34,6 +34,8 @@ def get_args(argv=None):
         p.add_argument("--checkpoint", required=True, help="the state_dict to score, as torch.save wrote it")
         p.add_argument("--bert_name_or_path", default="bert-chinese-base",
                        help="local directory holding the BERT's config.json and vocab.txt")
+        p.add_argument("--dtype", choices=("f32", "bf16", "f16"), default="f32",
+                       help="operands of the encoder's Linears (FrontendModel.set_dtype); f32 accumulation throughout")
         if name == "cv":
             p.add_argument("--cv_polyphone_data", required=True, help="polyphone lines of the validation set")
             p.add_argument("--cv_prosody_data", required=True, help="prosody lines of the validation set")
@@ -62,7 +64,7 @@ def run(args):
     else:
         data = FrontendDataset(tokenizer, prosody_file=args.test_data, prosody_dict=prosody_dict)
     model = FrontendModel(len(polyphone_dict), len(prosody_dict), os.path.join(args.bert_name_or_path, "config.json"),
-                          bert_name_or_path=args.bert_name_or_path)
+                          bert_name_or_path=args.bert_name_or_path).set_dtype(getattr(args, "dtype", "f32"))
     model.load_state_dict(torch.load(args.checkpoint, map_location="cpu", weights_only=True)).to("cuda")
     loader = _batches(data, args.batch_size, tokenizer)
     w = args.polyphone_weight if args.command == "cv" else 0.5
