@@ -905,6 +905,67 @@ int32_t wetts_frontend_score_heads(const wetts_frontend_t* f, const float* x, co
                                    float* losses, int64_t* counts, void* workspace, int64_t workspace_bytes,
                                    int32_t* status, void* stream);
 
+/* ---- training the text frontend (csrc/frontend_train.hip) -----------------------------------------------------------
+ * The other half of frontend/train.py: the gradient of the loss of train.py:71-84 (loss.backward(), :99) and
+ * torch.optim.AdamW's step (:184, :100).  What is trained is what the reference trains (frontend/model.py:30-31 freezes
+ * BERT): the 12 `transform.*` tensors and the 4 classifier tensors, the contiguous tail of the blob.  float32 only; the
+ * forward pass is the dropout-free one wetts_frontend_forward / _score compute (the reference's model.train() turns on
+ * p = 0.1 dropout, whose masks come from torch's generator: out of scope).  No atomics on floats: the same call gives
+ * the same bits, and they do not depend on what padded tokens hold. */
+/* The trainable tail of the blob (model.py:30-31): *offset = the first float of transform.self_attn.in_proj_weight,
+ * *numel = everything from there to the blob's end, alignment padding included. */
+int32_t wetts_frontend_trainable_span(const wetts_frontend_config_t* cfg, int64_t* offset, int64_t* numel);
+/* Bytes of scratch wetts_frontend_grad needs for B rows of T tokens (T <= 512); negative on a bad argument. */
+int64_t wetts_frontend_train_workspace_bytes(const wetts_frontend_t* f, int32_t B, int32_t T);
+/* train.py:71-84 and :99 on one batch: forward, loss, backward.  `grad`: the gradients in the blob's own layout of the
+ * trainable span (numel floats, 16-byte aligned; its alignment padding is zeroed).  losses / counts / nll_* / pred_* /
+ * status: wetts_frontend_score's own outputs from its own launches (the losses are bit-identical to it; nll_* and
+ * pred_* may be null).  loss = w phone + (1 - w) prosody with w = polyphone_weight (train.py:83-84).  A head without a
+ * scored label reports NaN as wetts_frontend_score does and contributes ZERO gradient (the reference's 0 / 0 would
+ * destroy the model); labels flagged LABEL_RANGE / LABEL_AT_PAD are not scored and contribute none.  Allocates nothing
+ * and does not synchronise. */
+int32_t wetts_frontend_grad(const wetts_frontend_t* f, const int64_t* input_ids, const int64_t* token_type_ids,
+                            const int64_t* attention_mask, const int64_t* phone_labels, const int64_t* prosody_labels,
+                            int32_t B, int32_t T, double polyphone_weight, float* grad, float* losses, int64_t* counts,
+                            float* nll_phone, float* nll_prosody, int32_t* pred_phone, int32_t* pred_prosody,
+                            void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+/* torch.optim.AdamW's single-tensor step (train.py:184 at its defaults, :100) on the handle's trainable span in place:
+ * p *= 1 - lr wd; m, v updated; p -= (lr / bias_correction1) m / (sqrt(v) / sqrt(bias_correction2) + eps).  grad, m, v:
+ * the span's layout.  The caller forms lr (the schedule of train.py:185-190), bias_correction1 = 1 - beta1^t and
+ * bias_correction2 = 1 - beta2^t in double.  wetts_frontend_adamw is the same launch on given buffers (numel % 4 == 0). */
+int32_t wetts_frontend_adamw_step(wetts_frontend_t* f, const float* grad, float* m, float* v, double lr, double beta1,
+                                  double beta2, double eps, double weight_decay, double bias_correction1,
+                                  double bias_correction2, void* stream);
+int32_t wetts_frontend_adamw(float* p, const float* grad, float* m, float* v, int64_t numel, double lr, double beta1,
+                             double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2,
+                             void* stream);
+/* Copies floats [offset, offset + numel) of the handle's blob to `out` (device), on the stream (train.py:215 saves them). */
+int32_t wetts_frontend_read_weights(const wetts_frontend_t* f, int64_t offset, int64_t numel, float* out, void* stream);
+/* The stages of the backward pass alone, each the launch the pass uses (loss.backward(), train.py:99).
+ * _linear_dgrad: dx [N][K] = dy [N][M] (row stride ldy) weight [M][K]; epilogue 0 none, 1 zero where aux [N][K] <= 0
+ *   (the ReLU mask from the saved activation), 2 + aux [N][K] (the residual's gradient).
+ * _linear_wgrad: dw [M][K] = dy^T x over the N tokens, db [M] (may be null) = column sums of dy.
+ * _layer_norm_backward: y = LayerNorm(x) gamma + beta -> dx, dgamma, dbeta (the last two may be null);
+ *   workspace >= (align64(2 N) + ceil(N / 64) C) floats.
+ * _attention_backward: qkv [B T][3 d], ctx = wetts_frontend_attention's output, dctx its gradient -> dqkv [B T][3 d];
+ *   workspace >= 2 align64(B heads T T) floats.
+ * _ce_backward: dlogits [N][P + R] = w_head / counts[head] (softmax - onehot) at scored tokens, zeros elsewhere;
+ *   counts: wetts_frontend_score's 22 (device). */
+int32_t wetts_frontend_linear_dgrad(const float* dy, int64_t ldy, const float* weight, int32_t N, int32_t M, int32_t K,
+                                    int32_t epilogue, const float* aux, float* dx, void* stream);
+int64_t wetts_frontend_linear_wgrad_workspace_bytes(int32_t N, int32_t M, int32_t K);
+int32_t wetts_frontend_linear_wgrad(const float* dy, int64_t ldy, const float* x, int32_t N, int32_t M, int32_t K, float* dw,
+                                    float* db, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t wetts_frontend_layer_norm_backward(const float* dy, const float* x, const float* gamma, float eps, int32_t N,
+                                           int32_t C, float* dx, float* dgamma, float* dbeta, void* workspace,
+                                           int64_t workspace_bytes, void* stream);
+int32_t wetts_frontend_attention_backward(const float* qkv, const float* key_mask, const float* ctx, const float* dctx,
+                                          int32_t B, int32_t T, int32_t heads, int32_t dk, float* dqkv, void* workspace,
+                                          int64_t workspace_bytes, void* stream);
+int32_t wetts_frontend_ce_backward(const float* phone_logits, const float* prosody_logits, const float* key_mask,
+                                   const int64_t* phone_labels, const int64_t* prosody_labels, const int64_t* counts,
+                                   int32_t N, int32_t P, int32_t R, double polyphone_weight, float* dlogits, void* stream);
+
 /* ---- WavLM, its resampler and the WavLMDiscriminator (losses.py:63-153, model/discriminators.py:452-498;
  * csrc/wavlm.hip) ------------------------------------------------------------------------------------------------
  * transformers' WavLMModel in the `wavlm-base` / `wavlm-base-plus` architecture -- feat_extract_norm "group", no conv

@@ -17,6 +17,16 @@ from .mel_processing import (mel_spectrogram_torch, posterior_spectrogram, spec_
                              spectrogram_torch)
 from .wavlm import Resample, WavLM, load_wavlm  # noqa: F401
 
+
+def __getattr__(name):
+    # FrontendTrainer on first use: frontend_train is also a `python -m` program, which must not be imported beforehand
+    if name == "FrontendTrainer":
+        from .frontend_train import FrontendTrainer
+        return FrontendTrainer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+# (FrontendTrainer is reached through __getattr__ and left out of __all__: a star import must not import frontend_train)
 __all__ = ["SynthesizerTrn", "MultiPeriodDiscriminator", "MultiPeriodMultiResolutionDiscriminator",
            "DurationDiscriminatorV1", "DurationDiscriminatorV2", "duration_discriminator_from_hparams",
            "WavLMDiscriminator", "wavlm_discriminator_from_hparams", "WavLMLoss", "WavLM", "Resample", "load_wavlm",

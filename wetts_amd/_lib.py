@@ -71,6 +71,7 @@ _P = C.c_void_p
 _I32 = C.c_int32
 _I64 = C.c_int64
 _F = C.c_float
+_D = C.c_double
 _CFG = C.POINTER(Config)
 
 
@@ -237,6 +238,18 @@ SIGNATURES = {
     "wetts_frontend_score_workspace_bytes": (_I64, [_P, _I32, _I32]),
     "wetts_frontend_score": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "wetts_frontend_score_heads": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "wetts_frontend_trainable_span": (_I32, [_FCFG, C.POINTER(_I64), C.POINTER(_I64)]),
+    "wetts_frontend_train_workspace_bytes": (_I64, [_P, _I32, _I32]),
+    "wetts_frontend_grad": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "wetts_frontend_adamw_step": (_I32, [_P, _P, _P, _P, _D, _D, _D, _D, _D, _D, _D, _P]),
+    "wetts_frontend_adamw": (_I32, [_P, _P, _P, _P, _I64, _D, _D, _D, _D, _D, _D, _D, _P]),
+    "wetts_frontend_read_weights": (_I32, [_P, _I64, _I64, _P, _P]),
+    "wetts_frontend_linear_dgrad": (_I32, [_P, _I64, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "wetts_frontend_linear_wgrad_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "wetts_frontend_linear_wgrad": (_I32, [_P, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
+    "wetts_frontend_layer_norm_backward": (_I32, [_P, _P, _P, _F, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "wetts_frontend_attention_backward": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
+    "wetts_frontend_ce_backward": (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _D, _P, _P]),
     "wetts_frontend_set_precision": (_I32, [_P, _I32]),
     "wetts_frontend_get_precision": (_I32, [_P]),
     "wetts_frontend_linear16_form": (_I32, [_I32, _I32]),

@@ -544,7 +544,11 @@ static FeLayout fe_layout(const wetts_frontend_config_t* c) {
   return l;
 }
 
-static int32_t fe_launch_linear(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int K,
+int64_t fe_tensor_offset(const wetts_frontend_config_t* c, const char* name) {
+  return name ? fe_layout(c).off(name) : fe_layout(c).total;
+}
+
+int32_t fe_launch_linear(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int K,
                                 int M, int epi, hipStream_t s) {
   WETTS_REQUIRE(x && w && bias && y && N >= 1, "frontend linear: bad argument (N=%d)", N);
   WETTS_REQUIRE(K >= 8 && K % 8 == 0 && M >= 4 && M % 4 == 0, "frontend linear: K=%d must be a multiple of 8, M=%d of 4", K, M);
@@ -562,7 +566,7 @@ static int32_t fe_launch_linear(const float* x, const float* w, const float* bia
   return WETTS_OK;
 }
 
-static int32_t fe_launch_add_ln(const float* x, const float* res, const float* gamma, const float* beta, float eps, int N,
+int32_t fe_launch_add_ln(const float* x, const float* res, const float* gamma, const float* beta, float eps, int N,
                                 int C, float* out, hipStream_t s) {
   WETTS_REQUIRE(x && gamma && beta && out && N >= 1, "frontend layer norm: bad argument (N=%d)", N);
   WETTS_REQUIRE(C >= 4 && C % 4 == 0 && C <= kFeMaxC, "frontend layer norm: C=%d must be a multiple of 4 up to %d", C, kFeMaxC);
@@ -571,7 +575,7 @@ static int32_t fe_launch_add_ln(const float* x, const float* res, const float* g
   return WETTS_OK;
 }
 
-static int32_t fe_launch_attention(const float* qkv, const float* maskf, float* ctx, int B, int T, int H, int dk,
+int32_t fe_launch_attention(const float* qkv, const float* maskf, float* ctx, int B, int T, int H, int dk,
                                    hipStream_t s) {
   WETTS_REQUIRE(qkv && maskf && ctx, "frontend attention: null argument");
   WETTS_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && T <= kFeMaxT, "frontend attention: B=%d, T=%d (at most %d)", B, T, kFeMaxT);
@@ -584,7 +588,7 @@ static int32_t fe_launch_attention(const float* qkv, const float* maskf, float* 
   return WETTS_OK;
 }
 
-static int32_t fe_launch_heads(const wetts_frontend* h, const float* x, const float* maskf, int N, int softmax, float* phone,
+int32_t fe_launch_heads(const wetts_frontend* h, const float* x, const float* maskf, int N, int softmax, float* phone,
                                float* prosody, hipStream_t s) {
   WETTS_REQUIRE(x && maskf && phone && prosody && N >= 1, "frontend heads: bad argument (N=%d)", N);
   hipLaunchKernelGGL(fe_heads_kernel, dim3((unsigned)cdiv(N, 4)), dim3(64 * kFeHeadWaves), 0, s, x, maskf, h->wp, h->bp, h->wr, h->br, N,
@@ -593,7 +597,7 @@ static int32_t fe_launch_heads(const wetts_frontend* h, const float* x, const fl
   return WETTS_OK;
 }
 
-static int32_t fe_launch_embed(const wetts_frontend* h, const int64_t* ids, const int64_t* tts, const int64_t* mask, int B,
+int32_t fe_launch_embed(const wetts_frontend* h, const int64_t* ids, const int64_t* tts, const int64_t* mask, int B,
                                int T, float* out, float* maskf, int32_t* status, hipStream_t s) {
   WETTS_REQUIRE(ids && out && maskf, "frontend embeddings: null argument");
   WETTS_REQUIRE(B >= 1 && T >= 1 && (int64_t)B * T <= 0x7fffffff / 4, "frontend: B=%d or T=%d out of range", B, T);
@@ -618,7 +622,7 @@ static void fe_regions(const wetts_frontend_config_t& c, int B, int T, int64_t o
 
 // one post-norm layer on h (in place); h2, ctx, qkv, ff are scratch.  prec != 0: the four Linears read 16-bit operands
 // (frontend16.hip); everything between them is the f32 code of prec == 0.
-static int32_t fe_run_block(const FeBlock& k, int d, float* h, float* h2, float* ctx, float* qkv, float* ff,
+int32_t fe_run_block(const FeBlock& k, int d, float* h, float* h2, float* ctx, float* qkv, float* ff,
                             const float* maskf, int B, int T, int prec, hipStream_t s) {
   const int N = B * T;
   auto linear = [&](const float* x, const float* w, const unsigned short* w16, const float* bias, const float* res, float* y,
@@ -644,6 +648,12 @@ int64_t fe_workspace_floats(const wetts_frontend* h, int B, int T) {
 
 int32_t fe_hidden(const wetts_frontend* h, const int64_t* ids, const int64_t* tts, const int64_t* mask, int B, int T,
                   void* workspace, int32_t* status, hipStream_t s, const char* what, const float** x, const float** maskf) {
+  return fe_hidden_layers(h, (int)h->blocks.size(), ids, tts, mask, B, T, workspace, status, s, what, x, maskf);
+}
+
+int32_t fe_hidden_layers(const wetts_frontend* h, int layers, const int64_t* ids, const int64_t* tts, const int64_t* mask,
+                         int B, int T, void* workspace, int32_t* status, hipStream_t s, const char* what, const float** x,
+                         const float** maskf) {
   WETTS_REQUIRE(B >= 1 && T >= 1, "%s: B=%d and T=%d must be at least 1", what, B, T);
   WETTS_REQUIRE(T <= h->cfg.max_position_embeddings && T <= kFeMaxT, "%s: T=%d exceeds the %d positions", what, T,
                 h->cfg.max_position_embeddings < kFeMaxT ? h->cfg.max_position_embeddings : kFeMaxT);
@@ -653,7 +663,8 @@ int32_t fe_hidden(const wetts_frontend* h, const int64_t* ids, const int64_t* tt
   float* ws = (float*)workspace;
   float *hb = ws + off[0], *h2 = ws + off[1], *ctx = ws + off[2], *qkv = ws + off[3], *ff = ws + off[4], *mf = ws + off[5];
   WETTS_TRY(fe_launch_embed(h, ids, tts, mask, B, T, hb, mf, status, s));
-  for (const FeBlock& k : h->blocks) WETTS_TRY(fe_run_block(k, h->cfg.hidden_size, hb, h2, ctx, qkv, ff, mf, B, T, h->precision, s));
+  for (int i = 0; i < layers && i < (int)h->blocks.size(); ++i)
+    WETTS_TRY(fe_run_block(h->blocks[i], h->cfg.hidden_size, hb, h2, ctx, qkv, ff, mf, B, T, h->precision, s));
   *x = hb;
   *maskf = mf;
   return WETTS_OK;

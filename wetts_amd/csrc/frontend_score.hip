@@ -277,13 +277,13 @@ fe_score_reduce_kernel(const float* __restrict__ maskf, const int64_t* __restric
 }
 
 // bytes of the scoring scratch: the records [tiles][Npad], then nll [2][Npad] f32 and pred [2][Npad] int32
-static int64_t fs_bytes(const wetts_frontend_config_t& c, int B, int T, int64_t* npad) {
+int64_t fs_bytes(const wetts_frontend_config_t& c, int B, int T, int64_t* npad) {
   const int64_t Np = align_up((int64_t)B * T, kFeNT);
   if (npad) *npad = Np;
   return ((int64_t)(cdiv(c.num_polyphones, 32) + cdiv(c.num_prosody, 32)) * 16 + 16) * Np;
 }
 
-static int32_t fs_launch(const wetts_frontend* h, const float* x, const float* maskf, const int64_t* lab_p,
+int32_t fs_launch(const wetts_frontend* h, const float* x, const float* maskf, const int64_t* lab_p,
                          const int64_t* lab_r, int B, int T, float* nll_p, float* nll_r, int32_t* pred_p, int32_t* pred_r,
                          float* losses, int64_t* counts, void* workspace, int64_t workspace_bytes, int32_t* status,
                          hipStream_t s) {

@@ -6,7 +6,7 @@ graph's session (frontend/export_onnx.py:72-91), cli/frontend.py's `Frontend` an
     phonemes, audio = model.synthesis("今天天气怎么样", "default")
 
 Everything between the string and the samples runs in csrc/frontend.hip and the existing synthesis path; there is no
-CPU inference, no onnxruntime and no `transformers` import.  Evaluation only (no gradients).
+CPU inference, no onnxruntime and no `transformers` import.  Evaluation only; training is frontend_train.FrontendTrainer.
 
 Padded positions: the reference leaves whatever its torch build computes at a token whose attention_mask is 0; here both
 outputs are ZEROS there."""
@@ -92,6 +92,7 @@ class FrontendModel:
         self._device = None
         self._status = None
         self._precision = 0
+        self._stale = False  # the device weights are newer than _blob (FrontendTrainer.step sets it)
 
     # ---- nn.Module-like surface ----
     def eval(self):
@@ -106,13 +107,15 @@ class FrontendModel:
         """What frontend/train.py:215 saves.  Every tensor the model reads must be present with its shape; the pooler
         and position_ids are ignored."""
         self._blob = checkpoint.pack_frontend_blob(self.config, state_dict)
+        self._stale = False
         if self._device is not None:
             self._create()
         return self
 
     def state_dict(self):
-        """The tensors the model uses, reference-keyed."""
+        """The tensors the model uses, reference-keyed (after FrontendTrainer.step: the trained ones, read back here)."""
         self._require_blob()
+        self._sync_blob()
         return {name: self._blob[off:off + numel].reshape(shape).clone()
                 for name, off, numel, shape in checkpoint.frontend_layout(self.config)}
 
@@ -155,7 +158,23 @@ class FrontendModel:
         if self._blob is None:
             raise RuntimeError("no weights: call load_state_dict() first")
 
+    def _sync_blob(self):
+        """Brings the trainable tail of _blob up to date with the device after training (one copy)."""
+        if not self._stale or self._handle is None:
+            return
+        lib = _lib.load()
+        off, num = C.c_int64(), C.c_int64()
+        cfg = checkpoint.frontend_c_config(self.config)
+        _lib.check(lib.wetts_frontend_trainable_span(C.byref(cfg), C.byref(off), C.byref(num)), "frontend_trainable_span")
+        with torch.cuda.device(self._device):
+            dev = torch.empty(num.value, dtype=torch.float32, device=self._device)
+            _lib.check(lib.wetts_frontend_read_weights(self._handle, off.value, num.value, _lib.ptr(dev),
+                                                       _lib.current_stream_ptr()), "frontend_read_weights")
+            self._blob[off.value:off.value + num.value] = dev.cpu()
+        self._stale = False
+
     def _create(self):
+        self._sync_blob()
         self._destroy()
         lib = _lib.load()
         with torch.cuda.device(self._device):
