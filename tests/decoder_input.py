@@ -8,7 +8,15 @@ every (B, L) of the GPU sweep (SHAPES[config], both iSTFT heads for the Vocos co
 for this operation on the reference side.  REL_GATE / LOCAL_GATE are 4 x that floor: the MFMA tiles and the K-split small
 kernel sum K in another order than the CPU conv, and the floor is the worst of a few dozen draws of a random walk, not a
 bound.  tests/test_cpu_decoder_gate.py recomputes the floor of the cheap configs and holds the constants to 2 .. 8 x
-it, and proves that the local gate sees a dropped tap, a lost halo column and a lost bias span by a factor >= 10."""
+it, and proves that the local gate sees a dropped tap, a lost halo column and a lost bias span by a factor >= 10.
+
+The Vocos seam sweep has a second family of the same things, leaving the first as it is: SEAM_CONFIGS (the two Vocos
+configs plus four coverage configs kept here as dicts, COVERAGE), SEAM_SHAPES (frame counts around the 62-column seams of
+convnext_dwln_kernel at every junk width of the padded rows), WIDE_SHAPES (vits2_vocos_v1 at B = 32 where pw_schedule
+gives pw_gemm_kernel blocks of several passes), SEAM_FLOOR / SEAM_FACTOR / SEAM_REL_GATE / SEAM_LOCAL_GATE measured over
+those shapes at their own seeds, and the head's geometry restated: dwln_tiles (tiles of the fused depthwise conv +
+LayerNorm), vocos_launches (launch_conv_small's take rule, pw_gemm_eligible and pw_schedule with the CU count as an
+argument: kernel, S, upb, pass widths and last unit per conv), pw_patterns and wide_claims (what a list of cases reaches)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -82,8 +90,93 @@ def vo():
     return vits_oracle
 
 
+# ---- the Vocos seam sweep: a second family of shapes, floors and gates (SHAPES / FLOOR / FACTOR above stay as they are) ---
+def _vocos_variant(channels, h_channels, n_fft, hop):
+    return dict(config.MODEL_CONFIGS["tiny_vocos"], vocos_channels=channels, vocos_h_channels=h_channels,
+                vocos_out_channels=n_fft + 2, vocos_num_layers=2,
+                vocos_istft_config=dict(n_fft=n_fft, hop_length=hop, win_length=n_fft, center=True))
+
+
+# Coverage configs of the seam sweep (two ConvNeXt layers, small n_fft: a float64 decode costs milliseconds).  They live
+# here and not in config.MODEL_CONFIGS, which other tests enumerate.  What each is for:
+#   vocos_c256  C = 256: convnext_dwln_kernel<16> and layernorm_reg_kernel<16>; h = 272 = 17 chunks of 16 (an odd number
+#               of chunks in pw_conv2's reduction); n_fft / hop = 2
+#   vocos_c96   C = 96 = 6 x 16, which k_convnext_dwln refuses: the k_dwconv + k_layernorm fallback; h = 176 = 11 chunks;
+#               n_fft / hop = 8
+#   vocos_c80   C = 80, no multiple of 32: pw_gemm_eligible refuses the residual conv (pw_conv2) and conv_mfma_kernel
+#               runs it with `res`; the fallback again (80 / 16 = 5); pw_conv1's reduction is 5 chunks; hop 24 does not
+#               divide n_fft 64
+#   vocos_n78   n_fft = 78: n_fft + 2 = 80 rows are whole chunks, k_rows_padded pads nothing; n_fft / hop = 3
+COVERAGE = {
+    "vocos_c256": _vocos_variant(256, 272, 64, 32),
+    "vocos_c96": _vocos_variant(96, 176, 64, 8),
+    "vocos_c80": _vocos_variant(80, 160, 64, 24),
+    "vocos_n78": _vocos_variant(64, 160, 78, 26),
+}
+SEAM_CONFIGS = ("tiny_vocos", "vocos_c256", "vocos_c96", "vocos_c80", "vocos_n78", "vits2_vocos_v1")
+
+# Frames F = L + 1 per config (row stride Fs = (F + 3) & ~3; convnext_dwln_kernel works in tiles of 62 columns of Fs):
+#   60 .. 66    the first seam 61 | 62 at all four junk widths Fs - F: 60 (one tile, 0 junk), 61 (Fs 64: the second tile
+#               holds columns 62, 63, junk only, 3 junk), 62 (F on the seam, second tile junk only, 2 junk), 63 (second tile:
+#               ONE valid column and one junk column), 64 (two valid, 0 junk), 65 (Fs 68, 3 junk), 66 (2 junk)
+#   122 .. 126  the second seam 123 | 124 likewise: 124 = 2 x 62 ends on it, 125 (Fs 128) leaves one valid column + 3 junk
+#   187         beyond the third seam 185 | 186: a fourth tile of one valid column and one junk column
+_SEAM_F_FULL = (60, 61, 62, 63, 64, 65, 66, 122, 123, 124, 125, 126, 187)
+_SEAM_F_SHORT = (61, 62, 63, 64, 124, 187)  # every junk width each side of the first seam, the second seam, four tiles
+_SEAM_F_BIG = (61, 62, 63, 64, 124)  # vits2_vocos_v1: what a few seconds of float64 oracle allow
+
+
+def _seam_grid(Bs, Fs_):
+    """(B, L) with B cycling through `Bs` by index."""
+    return tuple((Bs[i % len(Bs)], F_ - 1) for i, F_ in enumerate(Fs_))
+
+
+SEAM_SHAPES = {
+    "tiny_vocos": _seam_grid(_SMALL_B, _SEAM_F_FULL),
+    "vocos_c256": _seam_grid(_SMALL_B, _SEAM_F_FULL),
+    "vocos_c96": _seam_grid(_SMALL_B, _SEAM_F_SHORT),
+    "vocos_c80": _seam_grid(_SMALL_B, _SEAM_F_SHORT),
+    "vocos_n78": _seam_grid(_SMALL_B, _SEAM_F_SHORT),
+    "vits2_vocos_v1": _seam_grid(_BIG_B, _SEAM_F_BIG),
+}
+# vits2_vocos_v1 at the default dispatch, one utterance repeated B times, then B distinct ones: the (B, L) at which
+# pw_schedule (256 CUs) gives pw_gemm_kernel blocks of several passes (see vocos_launches; asserted in
+# tests/test_cpu_decoder_gate.py:test_wide_cases_reach_every_pass_pattern_of_pw_gemm).  The smallest L per pattern.
+#   32 x 128  Fs 132, 5 units, last of 4 columns: pw1 upb 3 = passes (2, 1) and (2): widths 2 and 1 in one block, S = 2
+#   32 x 192  Fs 196, 7 units: pw1 upb 4 = one 4-unit pass, then (2, 1); in / pw2 / iSTFT upb 2 with S = 4
+#   32 x 479  Fs 480 = 15 full units: pw1 upb 8 = (4, 4) and (4, 2, 1); in / out / iSTFT upb 4; pw2 (residual init) upb 2
+#   32 x 671  Fs 672 = 21 full units: pw1 upb 11 = (4, 4, 2, 1); pw2 upb 4 with the residual init; iSTFT upb 7 = (4, 2, 1)
+WIDE_CONFIG = "vits2_vocos_v1"
+WIDE_SHAPES = ((32, 128), (32, 192), (32, 479), (32, 671))
+SEAM_SEED, WIDE_SEED = 2000, 3000  # seed = base + index into SEAM_SHAPES[config] / WIDE_SHAPES
+
+# Worst (rel, local) of oracle-at-float32 against oracle-at-float64 over SEAM_SHAPES[config], both heads (seam_floor;
+# vits2_vocos_v1: also over row 0 of every wide case), measured on one CPU.  Gates = SEAM_FACTOR x these: the project's
+# 4, and the 6 of vits2_vocos_v1 for the reason written next to FACTOR (K = 1536 sums in MFMA order, spread evenly).
+# Measured on an MI355X (profiles/vocos_seam_margins.txt): every 4 x config stays under 0.37 of its gates in both forms;
+# vits2_vocos_v1 on pw_gemm_kernel (form tiled, and the wide cases at the default dispatch) reaches rel 3.3e-6 = 5.5 x
+# floor = 0.92 of its gate and local 1.7e-5 = 4.3 x floor, max|d| about 5 x rms(d): the same evenly spread error as
+# in the first sweep, at every pass pattern alike (32 x 128: 3.29e-6, 32 x 671: 3.27e-6), so no factor was raised.
+SEAM_FLOOR = {
+    "tiny_vocos": (4.71e-07, 2.98e-06),
+    "vocos_c256": (5.85e-07, 3.72e-06),
+    "vocos_c96": (6.09e-07, 3.27e-06),
+    "vocos_c80": (4.67e-07, 2.28e-06),
+    "vocos_n78": (4.52e-07, 2.79e-06),
+    "vits2_vocos_v1": (5.98e-07, 3.96e-06),
+}
+SEAM_FACTOR = dict({k: GATE_FACTOR for k in SEAM_FLOOR}, vits2_vocos_v1=FACTOR["vits2_vocos_v1"])
+SEAM_REL_GATE = {k: SEAM_FACTOR[k] * v[0] for k, v in SEAM_FLOOR.items()}
+SEAM_LOCAL_GATE = {k: SEAM_FACTOR[k] * v[1] for k, v in SEAM_FLOOR.items()}
+
+
+def model_dict(mname):
+    """The model section of a config: a coverage config of this file, or an entry of config.MODEL_CONFIGS."""
+    return dict(COVERAGE[mname] if mname in COVERAGE else config.MODEL_CONFIGS[mname])
+
+
 def model_cfg(mname):
-    return config.make_config(dict(config.MODEL_CONFIGS[mname]), N_VOCAB, N_SPK)
+    return config.make_config(model_dict(mname), N_VOCAB, N_SPK)
 
 
 def weights(mname, wseed=WSEED):
@@ -124,7 +217,7 @@ def gates(got, ref):
 
 def heads(mname):
     """The iSTFT heads a config is swept under: both for Vocos, the config's own (no effect) for HiFi-GAN."""
-    return (False, True) if mname in VOCOS else (None,)
+    return (False, True) if mname in VOCOS or mname in COVERAGE else (None,)
 
 
 def floor(mname, shapes=None):
@@ -139,6 +232,152 @@ def floor(mname, shapes=None):
             rel, loc = gates(oracle(W32, cd, z, g, head), oracle(W64, cd, z, g, head))
             worst = [max(worst[0], rel), max(worst[1], loc)]
     return tuple(worst)
+
+
+def seam_floor(mname, wide=False):
+    """Worst (rel, local) of the float32 oracle against the float64 oracle over SEAM_SHAPES[mname], both heads, at the
+    seam sweep's own seeds; `wide`: also over row 0 of every wide case (WIDE_CONFIG only)."""
+    cfg, sd, cd, W32, W64 = weights(mname)
+    cases = [(B, L, SEAM_SEED + i, B) for i, (B, L) in enumerate(SEAM_SHAPES[mname])]
+    if wide:
+        assert mname == WIDE_CONFIG
+        cases += [(B, L, WIDE_SEED + i, 1) for i, (B, L) in enumerate(WIDE_SHAPES)]
+    worst = [0.0, 0.0]
+    for B, L, seed, rows in cases:
+        z, g = inputs(W32, B, L, seed)
+        z, g = z[:rows], g[:rows]
+        for head in heads(mname):
+            rel, loc = gates(oracle(W32, cd, z, g, head), oracle(W64, cd, z, g, head))
+            worst = [max(worst[0], rel), max(worst[1], loc)]
+    return tuple(worst)
+
+
+# ---- geometry of the Vocos head (run_vocos in csrc/model.hip) restated; for choosing lengths, no kernel reads it --------
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def vocos_frames(L):
+    """(F, Fs): frames after nn.ReflectionPad1d([1, 0]) and the padded row stride of every [B][C][Fs] tensor."""
+    return L + 1, (L + 1 + 3) & ~3
+
+
+def dwln_tiles(C, L):
+    """convnext_dwln_kernel over one row of Fs columns (kernels.hip): 62 output columns per block.  `inst`: the
+    instantiation k_convnext_dwln picks (PER = C / 16 in {4, 16, 32}), None: it refuses and run_vocos falls back to
+    k_dwconv + k_layernorm (no tiles there; the same figures are kept so that the lengths can be judged alike).
+    `last_cols` / `last_valid`: stored / valid (< F) columns of the last tile; `junk` = Fs - F."""
+    F_, Fs = vocos_frames(L)
+    tiles = cdiv(Fs, 62)
+    inst = C // 16 if C % 16 == 0 and C // 16 in (4, 16, 32) else None
+    return dict(inst=inst, tiles=tiles, last_cols=Fs - 62 * (tiles - 1), last_valid=max(0, F_ - 62 * (tiles - 1)),
+                junk=Fs - F_, F=F_, Fs=Fs)
+
+
+def pw_schedule(strips, U, K, cus, slots=4):
+    """gemm_pw.hip:pw_schedule: (S blocks per strip, upb 32-column units per block) from the CU count."""
+    best, bestS = 1e30, 1
+    for S in range(1, U + 1):
+        upb = cdiv(U, S)
+        if S > 1 and cdiv(U, S - 1) == upb:
+            continue
+        blocks = strips * cdiv(U, upb)
+        per_cu = cdiv(blocks, cus)
+        npass = upb // 4 + (1 if upb % 4 >= 2 else 0) + (upb % 4 & 1)
+        block_cost = float(upb) * K + npass * (0.12 * K + 96.0)
+        block_cost += (2.0 * K * 0.08 if upb % 4 >= 2 else 0.0) + (1.0 * K * 0.20 if upb % 4 & 1 else 0.0)
+        resident = min(per_cu, slots)
+        eff = 1.0 if resident >= 3 else 0.85 if resident == 2 else 0.6
+        cost = float(per_cu) * block_cost / eff
+        if cost < best * 0.999:
+            best, bestS = cost, cdiv(U, upb)
+    return bestS, cdiv(U, bestS)
+
+
+def pw_passes(U, S, upb):
+    """The pass widths (4 / 2 / 1 units) of each of the S blocks of a strip, as pw_gemm_kernel walks them."""
+    out = []
+    for part in range(S):
+        u, u1, ws = part * upb, min(part * upb + upb, U), []
+        while u < u1:
+            w = 4 if u1 - u >= 4 else 2 if u1 - u >= 2 else 1
+            ws.append(w)
+            u += w
+        out.append(tuple(ws))
+    return tuple(out)
+
+
+def vocos_launches(mname, B, L, form, cus=256):
+    """The five kinds of conv launch of one Vocos decode of [B, 192, L] (in, pw1, pw2, out, istft; pw1 / pw2 once per
+    layer, all layers alike), form "default" (small_max_tiles = 256) or "tiled" (0): a restatement of launch_conv's
+    order -- launch_conv_small's take rule, then pw_gemm_eligible, else conv_mfma_kernel -- and of pw_schedule.  One
+    dict per conv: kernel ("small" / "pw_gemm" / "tiled"), M, K (the reduction in whole 16-channel chunks), N = Fs,
+    and for pw_gemm: S, upb, passes (per block of a strip), U, last_unit (stored columns of the last 32-column unit)
+    and last_valid (those of them in front of F)."""
+    m = model_dict(mname)
+    VC, VH, NF = m["vocos_channels"], m["vocos_h_channels"], m["vocos_istft_config"]["n_fft"]
+    VO = NF + 2
+    F_, Fs = vocos_frames(L)
+    small_max = 256 if form == "default" else 0
+    out = []
+    for name, M, Cin, res, padded in (("in", VC, m["inter_channels"], False, False), ("pw1", VH, VC, False, False),
+                                      ("pw2", VC, VH, True, False), ("out", VO, VC, False, False),
+                                      ("istft", NF, VO, False, True)):
+        nchunks = cdiv(Cin, 16)
+        r = dict(conv=name, M=M, K=nchunks * 16, N=Fs)
+        tiles64 = cdiv(M, 64) * cdiv(Fs, 64) * B
+        eligible = not (res and M % 32) and (Cin % 16 == 0 or padded) and Cin >= 32 and M * Fs * 4 < 2 ** 31 and \
+            nchunks * 16 * Fs * 4 < 2 ** 31  # (Fs % 4 == 0 and 256-byte aligned workspace tensors: the other terms hold)
+        if 0 < tiles64 <= small_max and nchunks >= 2:
+            r["kernel"] = "small"
+        elif eligible:
+            U = cdiv(Fs, 32)
+            S, upb = pw_schedule(B * cdiv(M, 128), U, nchunks * 16, cus)
+            r.update(kernel="pw_gemm", U=U, S=S, upb=upb, passes=pw_passes(U, S, upb), last_unit=Fs - 32 * (U - 1),
+                     last_valid=F_ - 32 * (U - 1))
+        else:
+            r["kernel"] = "tiled"
+        out.append(r)
+    return out
+
+
+def pw_patterns(cases, form, cus=256):
+    """What the pw_gemm launches of `cases` [(config, B, L)] reach: {conv: dict(widths, mixed, upb, split, partial,
+    full)} -- pass widths seen, a block of >= 2 passes of different width, the largest upb, S > 1 with upb > 1, a last
+    unit of fewer than 32 columns, a full last unit."""
+    acc = {}
+    for mname, B, L in cases:
+        for r in vocos_launches(mname, B, L, form, cus):
+            if r["kernel"] != "pw_gemm":
+                continue
+            e = acc.setdefault(r["conv"], dict(widths=set(), mixed=False, upb=0, split=False, partial=False, full=False))
+            for blk in r["passes"]:
+                e["widths"] |= set(blk)
+                e["mixed"] |= len(set(blk)) >= 2
+            e["upb"] = max(e["upb"], r["upb"])
+            e["split"] |= r["S"] > 1 and r["upb"] > 1
+            e["partial"] |= r["last_unit"] < 32
+            e["full"] |= r["last_unit"] == 32
+    return acc
+
+
+def wide_claims(cus):
+    """What the wide cases must reach on pw_gemm_kernel at the default dispatch with `cus` compute units: (patterns,
+    the claims that do NOT hold).  The CPU tier asserts them at 256 CUs, the GPU tier at the device's own count."""
+    pat = pw_patterns([(WIDE_CONFIG, B, L) for B, L in WIDE_SHAPES], "default", cus)
+    every = set().union(*(e["widths"] for e in pat.values())) if pat else set()
+    claims = {
+        "every conv (in, pw1, pw2, out, istft) runs on pw_gemm_kernel": set(pat) == {"in", "pw1", "pw2", "out", "istft"},
+        "pass widths 1, 2 and 4": every == {1, 2, 4},
+        "a block of passes of different width": any(e["mixed"] for e in pat.values()),
+        "upb >= 8": any(e["upb"] >= 8 for e in pat.values()),
+        "S > 1 together with upb > 1": any(e["split"] for e in pat.values()),
+        "a last unit of fewer than 32 columns": any(e["partial"] for e in pat.values()),
+        "a full last unit": any(e["full"] for e in pat.values()),
+        "a pass wider than one unit on the residual conv pw2": pat.get("pw2", {}).get("upb", 0) > 1,
+        "a pass wider than one unit on the padded-K iSTFT conv": pat.get("istft", {}).get("upb", 0) > 1,
+    }
+    return pat, [k for k, ok in claims.items() if not ok]
 
 
 # ---- tile geometry of the fused f32 ResBlock kernels (csrc/resblock32.hip, csrc/resblock_chain32.hip) ------------------
