@@ -4,8 +4,9 @@ measurement entry point wetts_bench_conv (wetts_amd/csrc/bench_conv.hip).
 
     python tools/bench_conv.py [variants]        variants: comma-separated ints, default "0,1"
 
-Variant 16 = fused pair / chain kernel, 32 = the same pair as two launches (pair mode); other values
-select a conv tile shape (WETTS_CONV_VARIANT).  Environment:
+Variant 16 = fused pair / chain kernel, 32 = the same pair as two launches (pair mode); 10 = the F(2,3)
+minimal-filtering form where the conv supports it; other values select a conv tile shape
+(WETTS_CONV_VARIANT).  Environment:
     WETTS_CONV_FLAGS=16|32   16-bit decoder kernels (bf16 | f16) instead of f32
     WETTS_PAIR=1             ResBlock1 pairs (c1 at dilation d, c2 at 1): compare variants 32 and 16
     WETTS_RB2=1              with WETTS_PAIR: ResBlock2 chains (both convs residual, c2 at 2d)
@@ -71,7 +72,8 @@ for (ch, k, d, L, fl) in shapes:
             row += f"  ERR {_lib.last_error()}"
             continue
         tf = (2 if pair else 1) * 2.0 * ch * ch * k * L * B / (ms.value * 1e-3) / 1e12
-        same = "" if ref is None else (" =" if abs(cs.value - ref) <= 1e-6 * max(1, abs(ref)) else " !=")
+        same = "" if ref is None else (" =" if abs(cs.value - ref) <= 1e-6 * max(1, abs(ref)) else
+                                       f" != ({abs(cs.value - ref) / max(1, abs(ref)):.0e})")
         ref = cs.value if ref is None else ref
         ntens = 5 if pair else (2 + (1 if fl & 2 else 0))  # per-conv algorithmic accounting
         gbs = ntens * ch * L * B * esz / (ms.value * 1e-3) / 1e9

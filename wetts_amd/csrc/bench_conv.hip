@@ -194,6 +194,7 @@ int32_t wetts_bench_conv(int32_t Cin, int32_t Cout, int32_t k, int32_t dil, int3
   WETTS_HIP_CHECK(hipMemsetAsync(o, 0, no * 4, s));
   PackedConv pc;
   WETTS_TRY(pack_conv_weight(w, bias, Cout, Cin, k, dil, (k * dil - dil) / 2, 0, 0, s, &pc));
+  if ((variant & 0xff) == 10) WETTS_TRY(pack_conv_f23(w, s, &pc));  // variant 10: the F(2,3) form (conv_mfma.hip)
   if (variant & 48) {  // ResBlock1 pair: 16 = fused kernel, 32 = two conv launches
     WETTS_REQUIRE(Cin == Cout, "pair bench needs Cin == Cout");
     PackedConv pc2;

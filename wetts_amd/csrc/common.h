@@ -182,6 +182,7 @@ struct PackedConv {
   int k_orig = 0;
   int off_lo = 0, span = 0, nchunks = 0;
   int gate_H = 0;          // > 0: M = 2 gate_H rows packed interleaved for OUT_GATE launches (only those)
+  float* wf23 = nullptr;   // device, the F(2,3) minimal-filtering pack (pack_conv_f23), or null: direct form only
 };
 
 // Packs a natural-layout weight into MFMA fragment order on the device.
@@ -193,6 +194,17 @@ int32_t pack_conv_weight(const float* w_dev, const float* bias_dev, int Cout, in
                          int dil, int pad, int transposed, int up, hipStream_t stream,
                          PackedConv* out, int rev_in = 0, int gate_H = 0);
 void free_packed(PackedConv* pc);
+// Adds the F(2,3) minimal-filtering pack of an already packed stride-1 Conv1d (conv_mfma.hip: the transformed taps
+// G0 .. G3 of every 3-tap group, computed in float64 from the f32 weights and rounded once).  Geometries the form does
+// not cover are left without one (pc->wf23 stays null), which is not an error.
+int32_t pack_conv_f23(const float* w_dev, hipStream_t stream, PackedConv* pc);
+// RAII: MRF launches of at least `min_tiles` 64x64 output tiles take the F(2,3) form on this thread where the conv has
+// the pack (0: wherever supported; outside a scope: never)
+struct ConvF23Scope {
+  explicit ConvF23Scope(int min_tiles);
+  ~ConvF23Scope();
+  int prev;
+};
 
 // Launches the conv.  Fills geometry fields of `p` from `pc`; caller fills the I/O fields.
 int32_t launch_conv(const PackedConv& pc, ConvParams p, hipStream_t stream);

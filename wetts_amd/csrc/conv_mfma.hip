@@ -119,6 +119,8 @@ int32_t pack_conv_weight(const float* w_dev, const float* bias_dev, int Cout, in
 void free_packed(PackedConv* pc) {
   if (pc->wpk) (void)hipFree(pc->wpk);
   pc->wpk = nullptr;
+  if (pc->wf23) (void)hipFree(pc->wf23);
+  pc->wf23 = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -684,6 +686,324 @@ void conv_mfma_group_kernel(const ConvGroupParams gp) {
   conv_mfma_body<MB, NB, WM, WN, EPI, true>(gp.p[j], bid - gp.first[j]);
 }
 
+// ------------------------------------------------------------------------------------------
+// F(2,3) minimal filtering (Winograd's form for a 3-tap group): two outputs from four products
+// instead of six.  Stride-1 dilated Conv1d with k in {3, 7, 11} taps at offsets (i - (k-1)/2) d.
+//
+// Pairs: outputs are paired by ABSOLUTE time -- pair P has the base t = P + d * (P / d), i.e.
+// (t mod 2d) < d, and the partner t + d -- whatever the tile, the batch row, `lens` or the launch
+// form.  A partner at or behind the row's end is computed and not stored.
+// Tap groups g = 0 .. k/3 - 1 cover taps 3g .. 3g + 2.  With a_j = a[t + off_{3g} + j d] (a = lrelu(x),
+// zero outside the row):  V0 = a0 - a2, V1 = a1 + a2, V2 = a2 - a1, V3 = a1 - a3  (one f32 rounding each);
+// G0 = w0, G1 = (w0 + w1 + w2) / 2, G2 = (w0 - w1 + w2) / 2, G3 = w2  (float64 from the f32 weights, rounded
+// once, at pack time);  m_q += G_q V_q;  y[t] = (m0 + m1) + m2,  y[t + d] = (m1 - m2) - m3.
+// A leftover tap i (k mod 3 of them) goes into m0 with w_i a[t + off_i] and into m3 with (-w_i) a[t + d + off_i].
+// Init: m0 = ((res + running sum) + bias)[t], m3 = -(the same at t + d), m1 = m2 = 0.
+// Accumulation order of every m_q (one sequential f32 fma chain each, as the MFMA runs it): 16-channel chunk ->
+// channel pair (k-step) -> group -> [leftover taps] -> the two channels of the pair.
+//
+// Wave tile: the four 32x32 accumulators of a wave are m0 .. m3 of the same 32 rows x 32 pairs, so the output
+// transform is lane-local.  Block: WM x WN waves = 32 WM rows x 32 WN pairs (64 WN output columns and up to d more:
+// the bases of 32 WN consecutive pairs span at most 64 WN + d - 2 columns).  Staging is the FAST staging of
+// conv_mfma_body (16-byte buffer loads, lrelu on the way into LDS); the transform is done at the B-fragment read:
+// k + 1 ds_reads (a3 of one group is a0 of the next; the leftover taps reuse them too), 4 VALU per group.
+// Packed A stream: [mt32][chunk][k-step 0..7][quad][lane][4], slot = quad * 4 + s: slots 4g + q = G_q of group g, then
+// (w_i, -w_i) per leftover tap, zero padded to whole quads; lane -> row = mt32 * 32 + (lane & 31),
+// ci = chunk * 16 + kstep * 2 + (lane >> 5).  Three zero k-steps behind the end (the prefetch is unconditional).
+// ------------------------------------------------------------------------------------------
+constexpr int f23_slots(int kt) { return 4 * (kt / 3) + 2 * (kt % 3); }
+constexpr int f23_quads(int kt) { return (f23_slots(kt) + 3) / 4; }
+constexpr int f23_stride(int wn) { return wn == 1 ? 160 : 224; }  // LDS row stride (= 32 mod 64, like the direct kernels')
+// pairs whose base lies in [0, n)
+__host__ __device__ inline int f23_pairs(int n, int d) { const int q = n / (2 * d), r = n - q * 2 * d; return q * d + (r < d ? r : d); }
+
+__global__ void pack_conv_f23_kernel(const float* __restrict__ w, float* __restrict__ out, int M, int Cin, int k,
+                                     int nchunks, int64_t total) {
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int ng = k / 3, S = 4 * ng + 2 * (k % 3), SQ = (S + 3) / 4;
+  const int s = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
+  int64_t rest = idx >> 8;
+  const int quad = (int)(rest % SQ);
+  rest /= SQ;
+  const int ks = (int)(rest & 7);
+  rest >>= 3;
+  const int chunk = (int)(rest % nchunks);
+  const int mt32 = (int)(rest / nchunks);
+  const int slot = quad * 4 + s;
+  const int row = mt32 * 32 + (lane & 31), ci = chunk * kConvCK + ks * 2 + (lane >> 5);
+  float v = 0.f;
+  if (row < M && ci < Cin && slot < S) {
+    const float* wr = w + ((int64_t)row * Cin + ci) * k;
+    if (slot < 4 * ng) {
+      const int g = slot >> 2, q = slot & 3;
+      const double w0 = wr[3 * g], w1 = wr[3 * g + 1], w2 = wr[3 * g + 2];
+      v = q == 0 ? wr[3 * g] : q == 1 ? (float)((w0 + w1 + w2) * 0.5) : q == 2 ? (float)((w0 - w1 + w2) * 0.5) : wr[3 * g + 2];
+    } else {
+      const int l = (slot - 4 * ng) >> 1;
+      v = wr[3 * ng + l];
+      if ((slot - 4 * ng) & 1) v = -v;
+    }
+  }
+  out[idx] = v;
+}
+
+int32_t pack_conv_f23(const float* w_dev, hipStream_t stream, PackedConv* pc) {
+  const int k = pc->ktaps;
+  if (pc->wf23 || pc->up != 0 || pc->gate_H != 0 || pc->dil < 1 || (k != 3 && k != 7 && k != 11) ||
+      pc->pad != (k - 1) / 2 * pc->dil || pc->Cin % kConvCK != 0 || pc->M % 64 != 0 || pc->wpk == nullptr)
+    return WETTS_OK;
+  const int SQ = f23_quads(k);
+  const int64_t total = (int64_t)(pc->M / 32) * pc->nchunks * 8 * SQ * 256, tail = (int64_t)3 * SQ * 256;
+  WETTS_HIP_CHECK(hipMalloc((void**)&pc->wf23, (total + tail) * sizeof(float)));
+  WETTS_HIP_CHECK(hipMemsetAsync(pc->wf23 + total, 0, (size_t)tail * sizeof(float), stream));
+  hipLaunchKernelGGL(pack_conv_f23_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w_dev, pc->wf23,
+                     pc->M, pc->Cin, k, pc->nchunks, total);
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
+template <int KT, int WM, int WN, int EPI>
+__device__ __forceinline__ void conv_f23_body(const ConvParams& p, int bid) {
+  static_assert(WM * WN == 4, "4 waves per block");
+  static_assert(EPI == 1 || EPI == 2, "plain store or the MRF mean");
+  constexpr int CK = kConvCK, RPW = CK / 4;
+  constexpr int NG = KT / 3, NL = KT % 3, SQ = f23_quads(KT);
+  constexpr int PT = 32 * WN, MT = 32 * WM, W = f23_stride(WN);
+
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+  const int half = lane >> 5;
+  const int d = p.dil;
+
+  // block -> (b, mtile, pair tile); pair tile fastest so neighbouring blocks share halos in L2
+  const int ntiles = (f23_pairs(p.N, d) + PT - 1) / PT;
+  const int mtiles = p.M / MT;
+  const int ptile = bid % ntiles;
+  bid /= ntiles;
+  const int mtile = bid % mtiles;
+  const int b = __builtin_amdgcn_readfirstlane(bid / mtiles);
+  const int P0 = ptile * PT;
+  const int n0 = P0 + d * (P0 / d);  // base of the block's first pair: the first output column it owns
+  int Tin = p.Tin;
+  if (p.lens) Tin = min((int)p.lens[b] * p.len_mul, p.Tin);
+  const int N = Tin;  // (stride 1, same padding: Tout == Tin)
+  if (n0 >= N) return;  // uniform per block
+
+  float* buf0 = smem;
+  float* buf1 = smem + CK * W;
+  const float* xb = p.x + (int64_t)b * p.x_bs;
+
+  // ---- FAST staging (conv_mfma_body's), one 16-byte piece per lane and row ------------------------
+  const int tstart = (n0 + p.off_lo) & ~3;  // first staged time (may be < 0)
+  const int sh = (n0 + p.off_lo) & 3;
+  const int W4 = min((2 * PT + 2 * d - 1 + p.span + sh + 3) >> 2, W / 4);  // pieces needed per row (the host checks the fit)
+  const int t0c = tstart < 0 ? 0 : tstart;
+  const int vbase = lane * 16 + (tstart - t0c) * 4;
+  const bool wrq = lane < W4;
+  const bool okq = wrq && tstart + 4 * lane >= 0 && tstart + 4 * lane + 4 <= Tin;
+  __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(xb), 0, __builtin_amdgcn_readfirstlane(((p.Cin - 1) * (int)p.x_cs + p.Tin) * 4), kBufRsrcDword3);
+  f32x4v stage4[RPW];
+  auto load_chunk = [&](int c) {
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      const int soff = __builtin_amdgcn_readfirstlane(((c * CK + wave + 4 * r) * (int)p.x_cs + t0c) * 4);
+      stage4[r] = f32x4v{0.f, 0.f, 0.f, 0.f};
+      if (okq) stage4[r] = __builtin_amdgcn_raw_buffer_load_b128(rsx, vbase, soff, 0);
+    }
+  };
+  auto store_chunk = [&](float* buf) {
+    const bool lr = p.in_act == IN_LRELU;
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      if (wrq) {
+        f32x4v v = stage4[r];
+        if (lr) {
+          v.x = lrelu2(v.x, p.in_slope);
+          v.y = lrelu2(v.y, p.in_slope);
+          v.z = lrelu2(v.z, p.in_slope);
+          v.w = lrelu2(v.w, p.in_slope);
+        }
+        *reinterpret_cast<f32x4v*>(buf + (wave + 4 * r) * W + 4 * lane) = v;
+      }
+    }
+  };
+
+  // this lane's pair
+  const int P = P0 + wn * 32 + (lane & 31);
+  const int tb = P + d * (P / d);
+  const bool ok0 = tb < N, ok1 = tb + d < N;
+  const int wrow0 = mtile * MT + wm * 32;  // first row of this wave (uniform)
+
+  // ---- accumulator init: m0 = ((res + running sum) + bias)[t], m3 = -(the same at t + d) ----------
+  f32x16 m0, m1, m2, m3;
+  {
+    const char* rbase = p.res ? reinterpret_cast<const char*>(p.res + (int64_t)b * p.r_bs + (int64_t)wrow0 * p.r_cs) : nullptr;
+    const char* pbase = reinterpret_cast<const char*>(p.out + (int64_t)b * p.o_bs + (int64_t)wrow0 * p.o_cs);
+    const unsigned rcs4 = (unsigned)p.r_cs * 4u, ocs4 = (unsigned)p.o_cs * 4u;
+    // every load unconditional and in flight at once (a column behind the row's end reads the block's first column instead:
+    // its value is never stored)
+    const unsigned c0 = (unsigned)(ok0 ? tb : n0) * 4u, c1 = (unsigned)(ok1 ? tb + d : n0) * 4u;
+    const unsigned rlane = (unsigned)(4 * half) * rcs4, olane = (unsigned)(4 * half) * ocs4;
+    const float* bp = p.bias ? p.bias + wrow0 + 4 * half : nullptr;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      m0[r] = 0.f;
+      m3[r] = 0.f;
+    }
+    if (rbase) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const unsigned rr = (unsigned)((r & 3) + 8 * (r >> 2));
+        m0[r] = *reinterpret_cast<const float*>(rbase + (rr * rcs4 + rlane + c0));
+        m3[r] = *reinterpret_cast<const float*>(rbase + (rr * rcs4 + rlane + c1));
+      }
+    }
+    if (p.accum) {
+      float pv[16][2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const unsigned rr = (unsigned)((r & 3) + 8 * (r >> 2));
+        pv[r][0] = *reinterpret_cast<const float*>(pbase + (rr * ocs4 + olane + c0));
+        pv[r][1] = *reinterpret_cast<const float*>(pbase + (rr * ocs4 + olane + c1));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        m0[r] += pv[r][0];
+        m3[r] += pv[r][1];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float bv = bp ? bp[(r & 3) + 8 * (r >> 2)] : 0.f;
+      m0[r] += bv;
+      m3[r] = -(m3[r] + bv);
+      m1[r] = 0.f;
+      m2[r] = 0.f;
+    }
+  }
+
+  // packed A stream of this wave's 32 rows: SQ quads per k-step, 8 k-steps per chunk.  The quads of k-step i live in
+  // register set i mod NS and are loaded NS - 1 k-steps ahead of their use (unconditionally: the k-steps behind the end
+  // are the next m-block's or the zero tail) -- about 12 ... 30 MFMAs, the L2 latency.
+  constexpr int NS = KT == 11 ? 2 : 4;
+  const float4* abase = reinterpret_cast<const float4*>(p.wpk) +
+                        ((int64_t)(mtile * WM + wm) * p.nchunks * 8 * SQ) * 64 + lane;
+  float4 aset[NS][SQ];
+#pragma unroll
+  for (int i = 0; i < NS - 1; ++i)
+#pragma unroll
+    for (int q = 0; q < SQ; ++q) aset[i][q] = abase[(i * SQ + q) * 64];
+#pragma unroll
+  for (int q = 0; q < SQ; ++q) aset[NS - 1][q] = aset[0][q];
+
+  load_chunk(0);
+  store_chunk(buf0);
+  __syncthreads();
+
+  const int cb = half * W + (tb - n0) + sh;  // this lane's LDS word of (k-step 0, tap offset 0)
+  int st = NS - 1;                           // the k-step the next prefetch loads
+  for (int c = 0; c < p.nchunks; ++c) {
+    const float* bl = ((c & 1) ? buf1 : buf0) + cb;
+    const bool more = (c + 1) < p.nchunks;
+    if (more) load_chunk(c + 1);
+    // raw B values a[t + off_0 + j d], j = 0 .. KT, of one k-step: read one k-step ahead of their use
+    float braw[2][KT + 1];
+#pragma unroll
+    for (int j = 0; j <= KT; ++j) braw[0][j] = bl[j * d];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+#pragma unroll
+      for (int q = 0; q < SQ; ++q) aset[(s + NS - 1) % NS][q] = abase[((int64_t)st * SQ + q) * 64];
+      ++st;
+      if (s < 7) {
+#pragma unroll
+        for (int j = 0; j <= KT; ++j) braw[(s + 1) & 1][j] = bl[2 * (s + 1) * W + j * d];
+      }
+      __builtin_amdgcn_sched_barrier(0);  // keep both prefetches ahead of this k-step's MFMAs
+      auto A = [&](int slot) {
+        const float4 v = aset[s % NS][slot >> 2];
+        return (slot & 3) == 0 ? v.x : (slot & 3) == 1 ? v.y : (slot & 3) == 2 ? v.z : v.w;
+      };
+      const float* a = braw[s & 1];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const float a0 = a[3 * g], a1 = a[3 * g + 1], a2 = a[3 * g + 2], a3 = a[3 * g + 3];
+        const float v0 = a0 - a2, v1 = a1 + a2, v2 = a2 - a1, v3 = a1 - a3;
+        m0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * g + 0), v0, m0, 0, 0, 0);
+        m1 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * g + 1), v1, m1, 0, 0, 0);
+        m2 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * g + 2), v2, m2, 0, 0, 0);
+        m3 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * g + 3), v3, m3, 0, 0, 0);
+      }
+#pragma unroll
+      for (int l = 0; l < NL; ++l) {  // leftover tap i = 3 NG + l: a[t + off_i] into m0, a[t + d + off_i] into m3
+        m0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 2 * l), a[3 * NG + l], m0, 0, 0, 0);
+        m3 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 2 * l + 1), a[3 * NG + l + 1], m3, 0, 0, 0);
+      }
+    }
+    if (more) store_chunk((c & 1) ? buf0 : buf1);
+    __syncthreads();
+  }
+
+  // ---- output transform and store (lane-local) ----------------------------------------------------
+  char* obase = reinterpret_cast<char*>(p.out + (int64_t)b * p.o_bs + (int64_t)wrow0 * p.o_cs);
+  const unsigned ocs4 = (unsigned)p.o_cs * 4u;
+  const unsigned olane = (unsigned)(4 * half) * ocs4 + (unsigned)tb * 4u;
+  const unsigned d4 = (unsigned)d * 4u;
+  // d = 1: the pair is two neighbouring samples at an even time, one 8-byte store
+  const bool vec2 = d == 1 && ((p.o_cs | p.o_bs) & 1) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 7) == 0;
+  auto store_all = [&](auto fin) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const unsigned roff = (unsigned)((r & 3) + 8 * (r >> 2)) * ocs4 + olane;
+      const float y0 = fin((m0[r] + m1[r]) + m2[r]);
+      const float y1 = fin((m1[r] - m2[r]) - m3[r]);
+      if (vec2 && ok1) {
+        float2 v;
+        v.x = y0;
+        v.y = y1;
+        *reinterpret_cast<float2*>(obase + roff) = v;
+      } else {
+        if (ok0) *reinterpret_cast<float*>(obase + roff) = y0;
+        if (ok1) *reinterpret_cast<float*>(obase + (roff + d4)) = y1;
+      }
+    }
+  };
+  if (EPI == 2) {  // the MRF mean (common.h: mrf_div)
+    const float dv = p.out_div, dinv = 1.f / p.out_div;
+    if (mrf_div_fast(dv)) store_all([=](float v) { return div_small_const(v, dv, dinv); });
+    else store_all([=](float v) { return v / dv; });
+  } else {
+    store_all([](float v) { return v; });
+  }
+}
+
+template <int KT, int WM, int WN, int EPI>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
+void conv_f23_mrf_kernel(const ConvParams p) {
+  conv_f23_body<KT, WM, WN, EPI>(p, blockIdx.x);
+}
+
+// the grouped entry: launch_conv_group's members in F(2,3) form, each block on its own member (k differs per member)
+template <int WM, int WN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
+void conv_f23_mrf_group_kernel(const ConvGroupParams gp) {
+  const int bid = blockIdx.x;
+  int j = 0;
+  if (gp.n > 1 && bid >= gp.first[1]) j = 1;
+  if (gp.n > 2 && bid >= gp.first[2]) j = 2;
+  const int kt = gp.p[j].ktaps;
+  if (kt == 3) conv_f23_body<3, WM, WN, 1>(gp.p[j], bid - gp.first[j]);
+  else if (kt == 7) conv_f23_body<7, WM, WN, 1>(gp.p[j], bid - gp.first[j]);
+  else conv_f23_body<11, WM, WN, 1>(gp.p[j], bid - gp.first[j]);
+}
+
 
 
 static bool conv_fast_ok(const ConvParams& p);
@@ -797,6 +1117,69 @@ static bool conv_fast_ok(const ConvParams& p) {
          ((int64_t)p.Cin * p.x_cs) < (1ll << 29) && (p.lens == nullptr || (p.len_mul & 3) == 0);
 }
 
+// ---- F(2,3) dispatch: by conv geometry and launch size only (the same answer for a conv whether it goes out alone,
+// in a group, forked, ragged or masked) -----------------------------------------------------------------------------
+static thread_local int tls_f23_min_tiles = INT32_MAX;
+ConvF23Scope::ConvF23Scope(int min_tiles) : prev(tls_f23_min_tiles) { tls_f23_min_tiles = min_tiles; }
+ConvF23Scope::~ConvF23Scope() { tls_f23_min_tiles = prev; }
+
+// `p` prepared (prepare_conv).  Variant 10 (micro-benchmark) and a threshold of 0 force the form wherever supported.
+static bool conv_f23_ok(const PackedConv& pc, const ConvParams& p) {
+  const int v = conv_variant();
+  if (v != 0 && v != 10) return false;
+  const int min_tiles = v == 10 ? 0 : tls_f23_min_tiles;
+  if (min_tiles == INT32_MAX || pc.wf23 == nullptr) return false;
+  const int wn = p.M % 128 == 0 ? 1 : 2;  // 128 rows x 32 pairs, else 64 rows x 64 pairs
+  const bool ok = p.up == 0 && p.out_act == OUT_NONE && p.out_mask == nullptr && p.wn_skip == nullptr &&
+                  p.bias_b == nullptr && p.tag && p.dil >= 1 && p.Tin == p.Tout && p.N == p.Tout && p.M % 64 == 0 &&
+                  conv_fast_ok(p) && 2 * 32 * wn + 2 * p.dil - 1 + p.span + 6 <= f23_stride(wn) &&
+                  // 32-bit byte offsets inside one utterance's 32-row slab of out / res
+                  ((int64_t)p.o_cs * 32 + p.Tout) * 4 < (1ll << 32) && ((int64_t)p.r_cs * 32 + p.Tout) * 4 < (1ll << 32);
+  if (!ok) return false;
+  // adopted per (C, k) class from the micro-benchmark (profiles/conv_f23_microbench.txt): every class but k = 3 below 128
+  // rows, whose 64 x 128 tile stages as much per MFMA as it saves (0.94 x at d = 1)
+  if (min_tiles > 0 && p.M < 128 && p.ktaps == 3) return false;
+  return (int64_t)cdiv(p.M, 64) * cdiv(p.N, 64) * p.B >= min_tiles;
+}
+
+template <int WM, int WN>
+static int32_t launch_f23_cfg(const PackedConv& pc, ConvParams p, hipStream_t stream) {
+  p.wpk = pc.wf23;
+  const int64_t blocks = (int64_t)cdiv(f23_pairs(p.N, p.dil), 32 * WN) * (p.M / (32 * WM)) * p.B;
+  if (blocks <= 0) return WETTS_OK;
+  WETTS_REQUIRE(blocks < (1ll << 31), "conv grid too large");
+  const size_t lds = (size_t)2 * kConvCK * f23_stride(WN) * sizeof(float);
+  const dim3 grid((unsigned)blocks), blk(256);
+#define WETTS_F23_LAUNCH(KT)                                                                                  \
+  if (p.out_div == 1.f) hipLaunchKernelGGL((conv_f23_mrf_kernel<KT, WM, WN, 1>), grid, blk, lds, stream, p); \
+  else hipLaunchKernelGGL((conv_f23_mrf_kernel<KT, WM, WN, 2>), grid, blk, lds, stream, p)
+  if (p.ktaps == 3) { WETTS_F23_LAUNCH(3); }
+  else if (p.ktaps == 7) { WETTS_F23_LAUNCH(7); }
+  else { WETTS_F23_LAUNCH(11); }
+#undef WETTS_F23_LAUNCH
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
+static int32_t launch_f23(const PackedConv& pc, const ConvParams& p, hipStream_t stream) {
+  return p.M % 128 == 0 ? launch_f23_cfg<4, 1>(pc, p, stream) : launch_f23_cfg<2, 2>(pc, p, stream);
+}
+
+template <int WM, int WN>
+static int32_t launch_f23_group_cfg(ConvGroupParams& gp, hipStream_t stream) {
+  int64_t total = 0;
+  for (int j = 0; j < gp.n; ++j) {
+    gp.first[j] = (int)total;
+    total += (int64_t)cdiv(f23_pairs(gp.p[j].N, gp.p[j].dil), 32 * WN) * (gp.p[j].M / (32 * WM)) * gp.p[j].B;
+  }
+  gp.first[gp.n] = (int)total;
+  WETTS_REQUIRE(total > 0 && total < (1ll << 31), "conv group grid size");
+  const size_t lds = (size_t)2 * kConvCK * f23_stride(WN) * sizeof(float);
+  hipLaunchKernelGGL((conv_f23_mrf_group_kernel<WM, WN>), dim3((unsigned)total), dim3(256), lds, stream, gp);
+  WETTS_LAUNCH_CHECK();
+  return WETTS_OK;
+}
+
 template <int MB, int NB, int WM, int WN>
 static int32_t launch_group_cfg(ConvGroupParams& gp, int max_span, hipStream_t stream) {
   constexpr int MT = 32 * MB * WM, NT = 32 * NB * WN;
@@ -823,6 +1206,49 @@ int32_t launch_conv_group(const PackedConv* const* pcs, const ConvParams* ps, in
   if (n <= 0) return WETTS_OK;
   ConvGroupParams gp;
   memset(&gp, 0, sizeof(gp));
+  if (n <= kConvGroupMax) {
+    // the members that take the F(2,3) form -- each decided as launch_conv decides for it alone -- go out as their own
+    // group (longest reduction first), the others as before
+    int fi[kConvGroupMax], ri[kConvGroupMax], nf = 0, nr = 0;
+    for (int j = 0; j < n; ++j) {
+      ConvParams q = ps[j];
+      WETTS_TRY(prepare_conv(*pcs[j], q));
+      if (conv_f23_ok(*pcs[j], q)) fi[nf++] = j; else ri[nr++] = j;
+    }
+    if (nf > 0) {
+      for (int a = 0; a < nf; ++a)
+        for (int b = a + 1; b < nf; ++b)
+          if (pcs[fi[b]]->ktaps > pcs[fi[a]]->ktaps) { int t = fi[a]; fi[a] = fi[b]; fi[b] = t; }
+      bool same = nf >= 2;
+      for (int j = 0; j < nf; ++j) {
+        gp.p[j] = ps[fi[j]];
+        WETTS_TRY(prepare_conv(*pcs[fi[j]], gp.p[j]));
+        gp.p[j].wpk = pcs[fi[j]]->wf23;
+        const ConvParams& q = gp.p[j];
+        same = same && q.out_div == 1.f && q.M == gp.p[0].M && q.N == gp.p[0].N && q.B == gp.p[0].B &&
+               q.Cin == gp.p[0].Cin && q.lens == gp.p[0].lens;
+      }
+      gp.n = nf;
+      int nl = nf;
+      if (same) {
+        nl = 1;
+        WETTS_TRY(gp.p[0].M % 128 == 0 ? (launch_f23_group_cfg<4, 1>(gp, stream)) : (launch_f23_group_cfg<2, 2>(gp, stream)));
+      } else {
+        for (int j = 0; j < nf; ++j) WETTS_TRY(launch_f23(*pcs[fi[j]], gp.p[j], stream));
+      }
+      if (nr > 0) {
+        const PackedConv* rp[kConvGroupMax];
+        ConvParams rps[kConvGroupMax];
+        for (int j = 0; j < nr; ++j) { rp[j] = pcs[ri[j]]; rps[j] = ps[ri[j]]; }
+        int rl = 0;
+        WETTS_TRY(launch_conv_group(rp, rps, nr, stream, &rl));
+        nl += rl;
+      }
+      if (launches) *launches = nl;
+      return WETTS_OK;
+    }
+    memset(&gp, 0, sizeof(gp));
+  }
   bool ok = n >= 2 && n <= kConvGroupMax && conv_variant() == 0;
   int order[kConvGroupMax] = {0, 1, 2};
   if (ok) {  // longest reduction first: the short members fill the tail of the long ones
@@ -860,6 +1286,8 @@ int32_t launch_conv_group(const PackedConv* const* pcs, const ConvParams* ps, in
 
 int32_t launch_conv(const PackedConv& pc, ConvParams p, hipStream_t stream) {
   WETTS_TRY(prepare_conv(pc, p));
+  // MRF single convs above the tile threshold: the F(2,3) minimal-filtering form (30 / 42 of the direct form's MFMAs)
+  if (conv_f23_ok(pc, p)) return launch_f23(pc, p, stream);
   // launches of at most ~one small tile per CU are latency-, not throughput-bound: own schedule
   if (conv_variant() == 0 && p.lens == nullptr) {
     bool taken = false;

@@ -724,11 +724,14 @@ __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const float* __rest
 // conv_post for launches too small to fill the chip (a streaming window is 15 k samples = 15 blocks of
 // the kernel above, each thread walking all C channels: 63 us, profiles/r02_b1_anatomy.txt): 8 channel
 // groups x 32 samples per block, the k-tap windows of a thread's C/8 channels loaded up front, partial
-// sums combined through LDS in a fixed order.
+// sums combined through LDS in a fixed order.  Ragged batches (lens) as in the kernel above: utterance b ends at
+// lens[b] * len_mul, the rest of its row reads as 0 and is written as 0 -- the same sums as the row alone, so a small
+// ragged launch and a small dense launch of one of its rows agree bit for bit.
 template <int K>
 __global__ __launch_bounds__(256) void conv_post_tanh_small_kernel(const float* __restrict__ x,
                                                                    const float* __restrict__ w, int B,
-                                                                   int C, int T, float* __restrict__ out) {
+                                                                   int C, int T, float* __restrict__ out,
+                                                                   const int64_t* __restrict__ lens, int len_mul) {
   constexpr int TL = 32, CG = 8, MAXC = 8;  // C <= 64
   __shared__ float red[CG][TL + 1];
   const int tl = threadIdx.x % TL, cg = threadIdx.x / TL;
@@ -737,6 +740,7 @@ __global__ __launch_bounds__(256) void conv_post_tanh_small_kernel(const float* 
   const int t = (blockIdx.x % tblocks) * TL + tl;
   constexpr int pad = (K - 1) / 2;
   const float* xb = x + (int64_t)b * C * T;
+  const int Tb = lens ? min((int)lens[b] * len_mul, T) : T;
   float win[MAXC][K], wv[MAXC][K];
 #pragma unroll
   for (int j = 0; j < MAXC; ++j) {
@@ -745,7 +749,7 @@ __global__ __launch_bounds__(256) void conv_post_tanh_small_kernel(const float* 
 #pragma unroll
     for (int i = 0; i < K; ++i) {
       const int tt = t - pad + i;
-      const bool ok = c < C && tt >= 0 && tt < T;
+      const bool ok = c < C && tt >= 0 && tt < Tb;
       win[j][i] = xb[(int64_t)cc * T + (ok ? tt : 0)];
       wv[j][i] = ok ? w[cc * K + i] : 0.f;
     }
@@ -764,7 +768,7 @@ __global__ __launch_bounds__(256) void conv_post_tanh_small_kernel(const float* 
     float tot = 0.f;
 #pragma unroll
     for (int q = 0; q < CG; ++q) tot += red[q][tl];
-    out[(int64_t)b * T + t] = tanhf(tot);
+    out[(int64_t)b * T + t] = t < Tb ? tanhf(tot) : 0.f;
   }
 }
 
@@ -773,9 +777,9 @@ int32_t k_conv_post_tanh(const float* x, const float* w, int k, int B, int C, in
   WETTS_REQUIRE(k <= 15, "conv_post kernel size %d unsupported", k);
   int64_t n = (int64_t)B * ((T + 3) / 4);
   if (n == 0) return WETTS_OK;
-  if (k == 7 && C <= 64 && n <= 64 * 256 && !lens) {  // fewer than 64 blocks of the kernel above
+  if (k == 7 && C <= 64 && n <= 64 * 256) {  // fewer than 64 blocks of the kernel above (dense and ragged alike)
     hipLaunchKernelGGL(conv_post_tanh_small_kernel<7>, dim3((unsigned)(B * cdiv(T, 32))), dim3(256), 0, s, x, w,
-                       B, C, T, out);
+                       B, C, T, out, lens, len_mul);
     WETTS_LAUNCH_CHECK();
     return WETTS_OK;
   }

@@ -498,6 +498,11 @@ struct wetts_model {
   int wn_fuse = 1;      // WETTS_TUNE wn_fuse: the f32 flow's residual / skip update in the res_skip conv's epilogue (1: small launches, 2: always, 0: wn_update_kernel)
   int small_fork = 1;   // WETTS_TUNE small_fork: the chains of a small (streaming-window) stage on their own streams
   int conv_groups = 1;  // WETTS_TUNE conv_groups: independent single convs of a ResBlock1 step in one launch (0: one each)
+  // WETTS_TUNE conv_f23_min_tiles: f32 MRF single convs of at least this many 64x64 output tiles run in the F(2,3)
+  // minimal-filtering form (conv_mfma.hip).  0: wherever the form is supported; INT32_MAX: never (no F(2,3) packs are made).
+  // 4096 = 1024 tiles of 128 x 128, the size from which launch_conv takes its big tile for the direct form: 2.7 rounds of
+  // the form's 128 x 64 blocks at three per CU.  The headline's stages are 6912 / 27648 / 27648 tiles.
+  int conv_f23_min_tiles = 4096;
   // MRF chains: the n_k ResBlocks of a stage are independent until their sum, so they run on
   // separate HIP streams (forked from / joined to the caller's stream with events); one chain's
   // launch tail and prologue/epilogue phases overlap another chain's MFMA work.
@@ -1087,6 +1092,7 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
         {"fuse2_waste_pct", &m->fuse2_waste_pct}, {"fuse_min_blocks", &m->fuse_min_blocks},
         {"chain_whole_pct", &m->chain_whole_waste_pct}, {"chain_whole_maxc", &m->chain_whole_maxc},
         {"small_max_tiles", &m->small_max_tiles}, {"attn_small_max_t", &m->attn_small_max_t},
+        {"conv_f23_min_tiles", &m->conv_f23_min_tiles},
     };
     if (const char* env = getenv("WETTS_TUNE")) {
       std::string all(env);
@@ -1117,6 +1123,15 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
           r = pack(m->layout, m->blob, S("flow.flows.%d.enc.in_layers.%d", flow_key_stride(cfg) * f, i), s,
                    &m->flows[f].in_layers[i]);
         }
+    }
+    if (r == WETTS_OK && m->conv_f23_min_tiles != INT32_MAX && cfg->vocoder_type != 1) {
+      // the F(2,3) packs of the ResBlock convs (the geometries the form does not cover stay without one)
+      for (const GenConv& g : hifigan_convs(cfg)) {
+        if (r != WETTS_OK || (g.kind != GenConv::C1 && g.kind != GenConv::C2)) continue;
+        ConvRef cr;
+        r = find_conv(m->layout, m->blob, g.prefix, &cr);
+        if (r == WETTS_OK) r = pack_conv_f23(cr.w, s, g.kind == GenConv::C1 ? &m->rbs[g.n].c1[g.d] : &m->rbs[g.n].c2[g.d]);
+      }
     }
     if (m->mrf_streams < 1) m->mrf_streams = 1;
     if (m->mrf_streams > cfg->n_resblock_kernels) m->mrf_streams = cfg->n_resblock_kernels;
@@ -2528,6 +2543,7 @@ static int32_t run_hifigan(const wetts_model* m, const float* z, int64_t z_bs, i
   const wetts_config_t* c = &m->cfg;
   const int I = c->inter_channels, C0 = c->upsample_initial_channel;
   const int64_t mx = dec_max_elems(c, B, L);
+  ConvF23Scope f23_scope(m->conv_f23_min_tiles);
   Bump ws(workspace, workspace_bytes);
   float* bx = ws.take<float>(mx);
   float* bt = ws.take<float>(mx);
