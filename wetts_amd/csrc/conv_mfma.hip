@@ -697,10 +697,15 @@ void conv_mfma_group_kernel(const ConvGroupParams gp) {
 // zero outside the row):  V0 = a0 - a2, V1 = a1 + a2, V2 = a2 - a1, V3 = a1 - a3  (one f32 rounding each);
 // G0 = w0, G1 = (w0 + w1 + w2) / 2, G2 = (w0 - w1 + w2) / 2, G3 = w2  (float64 from the f32 weights, rounded
 // once, at pack time);  m_q += G_q V_q;  y[t] = (m0 + m1) + m2,  y[t + d] = (m1 - m2) - m3.
-// A leftover tap i (k mod 3 of them) goes into m0 with w_i a[t + off_i] and into m3 with (-w_i) a[t + d + off_i].
+// One leftover tap i (k = 7) goes into m0 with w_i a[t + off_i] and into m3 with (-w_i) a[t + d + off_i].
+// Two leftover taps i, i + 1 (k = 11) are a 2-tap group in F(2,2) form, three products instead of four, on the same
+// accumulators: with a_j = a[t + off_i + j d]:  m0 += w_i (a0 - a1),  m1 += (w_i + w_{i+1}) a1,  m3 += w_{i+1} (a1 - a2)
+// (the sum of the two weights in float64, rounded once, at pack time; one f32 rounding per difference) -- (m0 + m1)
+// then carries w_i a0 + w_{i+1} a1 into y[t] and (m1 - m3) carries w_i a1 + w_{i+1} a2 into y[t + d]: the output
+// transform is unchanged.
 // Init: m0 = ((res + running sum) + bias)[t], m3 = -(the same at t + d), m1 = m2 = 0.
 // Accumulation order of every m_q (one sequential f32 fma chain each, as the MFMA runs it): 16-channel chunk ->
-// channel pair (k-step) -> group -> [leftover taps] -> the two channels of the pair.
+// channel pair (k-step) -> groups -> tail (the leftover taps) -> the two channels of the pair.
 //
 // Wave tile: the four 32x32 accumulators of a wave are m0 .. m3 of the same 32 rows x 32 pairs, so the output
 // transform is lane-local.  Block: WM x WN waves = 32 WM rows x 32 WN pairs (64 WN output columns and up to d more:
@@ -708,10 +713,11 @@ void conv_mfma_group_kernel(const ConvGroupParams gp) {
 // conv_mfma_body (16-byte buffer loads, lrelu on the way into LDS); the transform is done at the B-fragment read:
 // k + 1 ds_reads (a3 of one group is a0 of the next; the leftover taps reuse them too), 4 VALU per group.
 // Packed A stream: [mt32][chunk][k-step 0..7][quad][lane][4], slot = quad * 4 + s: slots 4g + q = G_q of group g, then
-// (w_i, -w_i) per leftover tap, zero padded to whole quads; lane -> row = mt32 * 32 + (lane & 31),
+// (w_i, -w_i) for one leftover tap or (w_i, w_i + w_{i+1}, w_{i+1}) for two, zero padded to whole quads (k = 3 / 7 / 11:
+// 4 / 10 / 15 slots in 1 / 3 / 4 quads); lane -> row = mt32 * 32 + (lane & 31),
 // ci = chunk * 16 + kstep * 2 + (lane >> 5).  Three zero k-steps behind the end (the prefetch is unconditional).
 // ------------------------------------------------------------------------------------------
-constexpr int f23_slots(int kt) { return 4 * (kt / 3) + 2 * (kt % 3); }
+__host__ __device__ constexpr int f23_slots(int kt) { return 4 * (kt / 3) + (kt % 3 == 2 ? 3 : 2 * (kt % 3)); }
 constexpr int f23_quads(int kt) { return (f23_slots(kt) + 3) / 4; }
 constexpr int f23_stride(int wn) { return wn == 1 ? 160 : 224; }  // LDS row stride (= 32 mod 64, like the direct kernels')
 // pairs whose base lies in [0, n)
@@ -721,7 +727,7 @@ __global__ void pack_conv_f23_kernel(const float* __restrict__ w, float* __restr
                                      int nchunks, int64_t total) {
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
-  const int ng = k / 3, S = 4 * ng + 2 * (k % 3), SQ = (S + 3) / 4;
+  const int ng = k / 3, S = f23_slots(k), SQ = (S + 3) / 4;
   const int s = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
   int64_t rest = idx >> 8;
   const int quad = (int)(rest % SQ);
@@ -739,6 +745,9 @@ __global__ void pack_conv_f23_kernel(const float* __restrict__ w, float* __restr
       const int g = slot >> 2, q = slot & 3;
       const double w0 = wr[3 * g], w1 = wr[3 * g + 1], w2 = wr[3 * g + 2];
       v = q == 0 ? wr[3 * g] : q == 1 ? (float)((w0 + w1 + w2) * 0.5) : q == 2 ? (float)((w0 - w1 + w2) * 0.5) : wr[3 * g + 2];
+    } else if (k % 3 == 2) {  // the F(2,2) tail: w_i, w_i + w_{i+1}, w_{i+1}
+      const int q = slot - 4 * ng;
+      v = q == 0 ? wr[3 * ng] : q == 1 ? (float)((double)wr[3 * ng] + (double)wr[3 * ng + 1]) : wr[3 * ng + 1];
     } else {
       const int l = (slot - 4 * ng) >> 1;
       v = wr[3 * ng + l];
@@ -941,10 +950,23 @@ __device__ __forceinline__ void conv_f23_body(const ConvParams& p, int bid) {
         m2 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * g + 2), v2, m2, 0, 0, 0);
         m3 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * g + 3), v3, m3, 0, 0, 0);
       }
-#pragma unroll
-      for (int l = 0; l < NL; ++l) {  // leftover tap i = 3 NG + l: a[t + off_i] into m0, a[t + d + off_i] into m3
-        m0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 2 * l), a[3 * NG + l], m0, 0, 0, 0);
-        m3 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 2 * l + 1), a[3 * NG + l + 1], m3, 0, 0, 0);
+      if (NL == 1) {  // leftover tap i = 3 NG: a[t + off_i] into m0, a[t + d + off_i] into m3
+        m0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG), a[3 * NG], m0, 0, 0, 0);
+        m3 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 1), a[3 * NG + 1], m3, 0, 0, 0);
+      } else if (NL == 2) {  // leftover taps 3 NG, 3 NG + 1 as one F(2,2) group: three products on m0, m1, m3
+        const float a0 = a[3 * NG], a1 = a[3 * NG + 1], a2 = a[3 * NG + 2];
+        const float u0 = a0 - a1, u3 = a1 - a2;
+        m0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 0), u0, m0, 0, 0, 0);
+        m1 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 1), a1, m1, 0, 0, 0);
+        m3 = __builtin_amdgcn_mfma_f32_32x32x2f32(A(4 * NG + 2), u3, m3, 0, 0, 0);
+      }
+      // The words of the last quad behind the last slot (k = 7: two, k = 11: one) are loaded and not used.  Left dead,
+      // their registers are handed to temporaries of the k-step while the 16-byte load that also writes them is in
+      // flight, and the write-after-write hazard costs an s_waitcnt vmcnt(0) right behind the prefetch: the whole L2
+      // latency, exposed every k-step.  Keep them allocated to here (no instruction is emitted).
+      if (f23_slots(KT) % 4 != 0) {
+        if (f23_slots(KT) % 4 <= 2) asm volatile("" : : "v"(aset[s % NS][SQ - 1].z));
+        asm volatile("" : : "v"(aset[s % NS][SQ - 1].w));
       }
     }
     if (more) store_chunk((c & 1) ? buf0 : buf1);
@@ -1286,7 +1308,7 @@ int32_t launch_conv_group(const PackedConv* const* pcs, const ConvParams* ps, in
 
 int32_t launch_conv(const PackedConv& pc, ConvParams p, hipStream_t stream) {
   WETTS_TRY(prepare_conv(pc, p));
-  // MRF single convs above the tile threshold: the F(2,3) minimal-filtering form (30 / 42 of the direct form's MFMAs)
+  // MRF single convs above the tile threshold: the F(2,3) minimal-filtering form (29 / 42 of the direct form's MFMAs)
   if (conv_f23_ok(pc, p)) return launch_f23(pc, p, stream);
   // launches of at most ~one small tile per CU are latency-, not throughput-bound: own schedule
   if (conv_variant() == 0 && p.lens == nullptr) {
