@@ -973,7 +973,9 @@ int32_t wetts_bench_mfma_valu(int32_t mode, int32_t nv, int32_t iters, double* t
 
 // ResBlock1 (k, dilations 1/3/5 in front of c1, c2 at 1) on [B,C,T], npairs = 1..3 pairs, at f32.
 // mode 0: conv by conv (2 launches per pair); 1: resblock_pair32_kernel per pair; 2: the chain kernel
-// per pair; 3: the chain kernel once for all pairs.  flags: 4 accumulate into out, 8 divide by 3.
+// per pair; 3: the chain kernel once for all pairs; 4 / 5: as 2 / 3 on resblock_chain_f23_kernel (the F(2,3) packs are made
+// here; an error where that kernel is not built for the shape -- its bits differ from conv by conv by design).
+// flags: 4 accumulate into out, 8 divide by 3.
 int32_t wetts_bench_resblock(int32_t C, int32_t k, int32_t npairs, int32_t first_dil, int32_t B, int32_t T,
                              int32_t flags, int32_t mode, int32_t iters, double* ms_out,
                              double* checksum_out) {
@@ -1002,7 +1004,11 @@ int32_t wetts_bench_resblock(int32_t C, int32_t k, int32_t npairs, int32_t first
     const int d = (i & 1) ? 1 : dils[i >> 1];
     WETTS_TRY(pack_conv_weight(w[i], bias[i], C, C, k, d, (k - 1) / 2 * d, 0, 0, s,
                                (i & 1) ? &c2[i >> 1] : &c1[i >> 1]));
+    if (mode >= 4) WETTS_TRY(pack_conv_f23(w[i], s, (i & 1) ? &c2[i >> 1] : &c1[i >> 1]));
   }
+  const bool f23 = mode >= 4;
+  if (f23) mode -= 2;
+  ChainF23Scope chain_f23_scope(f23 ? 0 : INT32_MAX);
   const int accum = (flags & 4) ? 1 : 0;
   const float odiv = (flags & 8) ? 3.f : 1.f;
   auto run = [&]() -> int32_t {
@@ -1010,6 +1016,7 @@ int32_t wetts_bench_resblock(int32_t C, int32_t k, int32_t npairs, int32_t first
       ResChain32Params cp;
       memset(&cp, 0, sizeof(cp));
       cp.x = x; cp.out = o; cp.T = T; cp.B = B; cp.accum = accum; cp.out_div = odiv; cp.slope = 0.1f;
+      if (f23) WETTS_REQUIRE(resblock_chain_f23_supported(c1, c2, npairs, cp), "F(2,3) chain kernel not built for this shape");
       return launch_resblock_chain32(c1, c2, npairs, cp, s);
     }
     const float* cur = x;
@@ -1021,6 +1028,7 @@ int32_t wetts_bench_resblock(int32_t C, int32_t k, int32_t npairs, int32_t first
         memset(&cp, 0, sizeof(cp));
         cp.x = cur; cp.out = dst; cp.T = T; cp.B = B; cp.accum = last ? accum : 0;
         cp.out_div = last ? odiv : 1.f; cp.slope = 0.1f;
+        if (f23) WETTS_REQUIRE(resblock_chain_f23_supported(&c1[pr], &c2[pr], 1, cp), "F(2,3) chain kernel not built for this shape");
         WETTS_TRY(launch_resblock_chain32(&c1[pr], &c2[pr], 1, cp, s));
       } else if (mode == 1) {
         ResPair32Params q;

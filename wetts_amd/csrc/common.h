@@ -198,6 +198,9 @@ void free_packed(PackedConv* pc);
 // G0 .. G3 of every 3-tap group, computed in float64 from the f32 weights and rounded once).  Geometries the form does
 // not cover are left without one (pc->wf23 stays null), which is not an error.
 int32_t pack_conv_f23(const float* w_dev, hipStream_t stream, PackedConv* pc);
+// A slots per k-step of the F(2,3) pack of a kt-tap conv, and the 16-byte quads that hold them (conv_mfma.hip)
+__host__ __device__ constexpr int f23_slots(int kt) { return 4 * (kt / 3) + (kt % 3 == 2 ? 3 : 2 * (kt % 3)); }
+constexpr int f23_quads(int kt) { return (f23_slots(kt) + 3) / 4; }
 // RAII: MRF launches of at least `min_tiles` 64x64 output tiles take the F(2,3) form on this thread where the conv has
 // the pack (0: wherever supported; outside a scope: never)
 struct ConvF23Scope {

@@ -717,8 +717,7 @@ void conv_mfma_group_kernel(const ConvGroupParams gp) {
 // 4 / 10 / 15 slots in 1 / 3 / 4 quads); lane -> row = mt32 * 32 + (lane & 31),
 // ci = chunk * 16 + kstep * 2 + (lane >> 5).  Three zero k-steps behind the end (the prefetch is unconditional).
 // ------------------------------------------------------------------------------------------
-__host__ __device__ constexpr int f23_slots(int kt) { return 4 * (kt / 3) + (kt % 3 == 2 ? 3 : 2 * (kt % 3)); }
-constexpr int f23_quads(int kt) { return (f23_slots(kt) + 3) / 4; }
+// (f23_slots, f23_quads: common.h -- resblock_chain_f23.hip reads the same pack)
 constexpr int f23_stride(int wn) { return wn == 1 ? 160 : 224; }  // LDS row stride (= 32 mod 64, like the direct kernels')
 // pairs whose base lies in [0, n)
 __host__ __device__ inline int f23_pairs(int n, int d) { const int q = n / (2 * d), r = n - q * 2 * d; return q * d + (r < d ? r : d); }
@@ -760,7 +759,7 @@ __global__ void pack_conv_f23_kernel(const float* __restrict__ w, float* __restr
 int32_t pack_conv_f23(const float* w_dev, hipStream_t stream, PackedConv* pc) {
   const int k = pc->ktaps;
   if (pc->wf23 || pc->up != 0 || pc->gate_H != 0 || pc->dil < 1 || (k != 3 && k != 7 && k != 11) ||
-      pc->pad != (k - 1) / 2 * pc->dil || pc->Cin % kConvCK != 0 || pc->M % 64 != 0 || pc->wpk == nullptr)
+      pc->pad != (k - 1) / 2 * pc->dil || pc->Cin % kConvCK != 0 || pc->M % 32 != 0 || pc->wpk == nullptr)
     return WETTS_OK;
   const int SQ = f23_quads(k);
   const int64_t total = (int64_t)(pc->M / 32) * pc->nchunks * 8 * SQ * 256, tail = (int64_t)3 * SQ * 256;

@@ -499,10 +499,17 @@ struct wetts_model {
   int small_fork = 1;   // WETTS_TUNE small_fork: the chains of a small (streaming-window) stage on their own streams
   int conv_groups = 1;  // WETTS_TUNE conv_groups: independent single convs of a ResBlock1 step in one launch (0: one each)
   // WETTS_TUNE conv_f23_min_tiles: f32 MRF single convs of at least this many 64x64 output tiles run in the F(2,3)
-  // minimal-filtering form (conv_mfma.hip).  0: wherever the form is supported; INT32_MAX: never (no F(2,3) packs are made).
+  // minimal-filtering form (conv_mfma.hip).  0: wherever the form is supported; INT32_MAX: never (the F(2,3) packs are
+  // made unless chain_f23_min_tiles is INT32_MAX too).
   // 4096 = 1024 tiles of 128 x 128, the size from which launch_conv takes its big tile for the direct form: 2.7 rounds of
   // the form's 128 x 64 blocks at three per CU.  The headline's stages are 6912 / 27648 / 27648 tiles.
   int conv_f23_min_tiles = 4096;
+  // WETTS_TUNE chain_f23_min_tiles: f32 ResBlock1 chain launches of at least this many 64x64 output tiles run on
+  // resblock_chain_f23_kernel where it is built (resblock_chain_f23.hip: C = 32, k = 7 / 11, one pair per launch).  Unit and
+  // conventions of conv_f23_min_tiles: 0 wherever built, INT32_MAX never.  The headline's chain launches are 24 512 -
+  // 49 024 tiles; the fused-vs-unfused bit-identity tests (at most 1600) stay on resblock_chain32_kernel, and must: the
+  // form computes other bits than the conv-by-conv path.
+  int chain_f23_min_tiles = 4096;
   // MRF chains: the n_k ResBlocks of a stage are independent until their sum, so they run on
   // separate HIP streams (forked from / joined to the caller's stream with events); one chain's
   // launch tail and prologue/epilogue phases overlap another chain's MFMA work.
@@ -1092,7 +1099,7 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
         {"fuse2_waste_pct", &m->fuse2_waste_pct}, {"fuse_min_blocks", &m->fuse_min_blocks},
         {"chain_whole_pct", &m->chain_whole_waste_pct}, {"chain_whole_maxc", &m->chain_whole_maxc},
         {"small_max_tiles", &m->small_max_tiles}, {"attn_small_max_t", &m->attn_small_max_t},
-        {"conv_f23_min_tiles", &m->conv_f23_min_tiles},
+        {"conv_f23_min_tiles", &m->conv_f23_min_tiles}, {"chain_f23_min_tiles", &m->chain_f23_min_tiles},
     };
     if (const char* env = getenv("WETTS_TUNE")) {
       std::string all(env);
@@ -1124,7 +1131,7 @@ int32_t wetts_create(const wetts_config_t* cfg, const float* blob_dev, int64_t b
                    &m->flows[f].in_layers[i]);
         }
     }
-    if (r == WETTS_OK && m->conv_f23_min_tiles != INT32_MAX && cfg->vocoder_type != 1) {
+    if (r == WETTS_OK && (m->conv_f23_min_tiles != INT32_MAX || m->chain_f23_min_tiles != INT32_MAX) && cfg->vocoder_type != 1) {
       // the F(2,3) packs of the ResBlock convs (the geometries the form does not cover stay without one)
       for (const GenConv& g : hifigan_convs(cfg)) {
         if (r != WETTS_OK || (g.kind != GenConv::C1 && g.kind != GenConv::C2)) continue;
@@ -2544,6 +2551,7 @@ static int32_t run_hifigan(const wetts_model* m, const float* z, int64_t z_bs, i
   const int I = c->inter_channels, C0 = c->upsample_initial_channel;
   const int64_t mx = dec_max_elems(c, B, L);
   ConvF23Scope f23_scope(m->conv_f23_min_tiles);
+  ChainF23Scope chain_f23_scope(m->chain_f23_min_tiles);
   Bump ws(workspace, workspace_bytes);
   float* bx = ws.take<float>(mx);
   float* bt = ws.take<float>(mx);

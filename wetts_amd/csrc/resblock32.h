@@ -60,7 +60,24 @@ struct ResChain32Params {
 bool resblock_chain32_supported(const PackedConv* c1, const PackedConv* c2, int npairs,
                                 int max_lds_bytes, int max_waste_pct);
 int resblock_chain32_nto(int C, int ktaps, const int* dil, int npairs);  // valid outputs per tile
+// The one entry of every chain launch.  Inside a ChainF23Scope, launches of at least its size whose geometry
+// resblock_chain_f23.hip is built for go to resblock_chain_f23_kernel; all others to resblock_chain32_kernel.
 int32_t launch_resblock_chain32(const PackedConv* c1, const PackedConv* c2, int npairs,
                                 ResChain32Params p, hipStream_t stream);
+
+// ---- the same pair in F(2,3) minimal-filtering form (resblock_chain_f23.hip; not bit-identical to the above) ----
+// RAII: chain launches of at least `min_tiles` 64x64 output tiles take the form on this thread where it is built and
+// both convs have the F(2,3) pack (0: wherever built; outside a scope: never)
+struct ChainF23Scope {
+  explicit ChainF23Scope(int min_tiles);
+  ~ChainF23Scope();
+  int prev;
+};
+// p: T, B, lens, len_mul filled.  supported: the geometry is built; take: and the scope's threshold admits the launch
+bool resblock_chain_f23_supported(const PackedConv* c1, const PackedConv* c2, int npairs, const ResChain32Params& p);
+bool resblock_chain_f23_take(const PackedConv* c1, const PackedConv* c2, int npairs, const ResChain32Params& p);
+// p as launch_resblock_chain32 prepares it (dil, bias, npairs, ktaps, bstride)
+int32_t launch_resblock_chain_f23(const PackedConv* c1, const PackedConv* c2, int npairs, ResChain32Params p,
+                                  hipStream_t stream);
 
 }  // namespace wetts

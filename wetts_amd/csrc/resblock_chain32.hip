@@ -488,6 +488,8 @@ int32_t launch_resblock_chain32(const PackedConv* c1, const PackedConv* c2, int 
     p.bias[2 * pr + 1] = c2[pr].bias;
     p.dil[pr] = c1[pr].dil;
   }
+  // the one place that chooses the kernel of a chain launch: by geometry and launch size only (resblock_chain_f23.hip)
+  if (resblock_chain_f23_take(c1, c2, npairs, p)) return launch_resblock_chain_f23(c1, c2, npairs, p, stream);
   int S_, Mmin_;
   chain_geometry(p.ktaps, p.dil, npairs, &S_, &Mmin_);
   const int nb = chain_nb(c1[0].Cin, Mmin_);
